@@ -20,6 +20,7 @@ import argparse
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -191,6 +192,26 @@ def es_generation_leg(env, world, rank, dist, barrier, max_step=400):
                         "all_gather of the returns, SimpleGA.tell"}
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """--dump-outputs: write `arrays` (name -> [N, ...] host array, one row per robot) as out_dir/<name><suffix>.npy in float32 /
+    float64.  Beyond DUMP_MAX_BYTES in all, a fixed sample of robots (default_rng(0), sorted) is written instead, with its row
+    indices as robot_index.npy, so that two builds given the same arguments write the same rows."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(v[:1].nbytes for v in arrays.values())
+    if n * row_bytes + 4096 * len(arrays) > DUMP_MAX_BYTES:
+        m = (DUMP_MAX_BYTES - 4096 * (len(arrays) + 1)) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["robot_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), v)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -200,7 +221,7 @@ def _free_port():
 
 
 def spawn_ranks(n):
-    """`python bench.py --gpus N` without a launcher: become `torch.distributed.run --nproc-per-node N bench.py ...`."""
+    """`python bench.py --gpus N` without a launcher: run `torch.distributed.run --nproc-per-node N bench.py ...` and exit with its code."""
     backend = os.environ.get("ETG_BENCH_BACKEND", "nccl")
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if backend == "nccl" and have < n:
@@ -210,7 +231,8 @@ def spawn_ranks(n):
            "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # a child process, not an exec: device_count() above may already have opened the HIP runtime in this one
+    raise SystemExit(subprocess.call(cmd))
 
 
 def main():
@@ -244,7 +266,12 @@ def main():
     ap.add_argument("--no-es-generation", action="store_true", help="skip only the ES-generation leg")
     ap.add_argument("--stepwise", action="store_true",
                     help="time env.step() per control step instead of the fused rollout")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in the last timed repeat (episode returns and "
+                         "lengths, observation and state rows; reward and done with --stepwise) as DIR/<name>.npy (e.g. DIR = bench_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     SOLVER = A.solver_rule(args.solver_iters, args.solver_residual)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -312,6 +339,7 @@ def main():
     stat_buf = (torch.empty(N, device=dev), torch.empty(N, dtype=torch.int32, device=dev))   # episode returns / lengths of a rollout
     wall_local = []      # this rank's own wall seconds of the last timed_repeats() call (before the max over ranks)
     live_steps = []      # this rank's env-steps of still-running episodes inside the timed region, per repeat of the last call
+    last_stats = []      # (episode returns, lengths) the timed steps of the last repeat returned
 
     step_groups = [1]     # sub-batches of the stepping legs (env.run_groups): 1 = one launch per control step
 
@@ -369,6 +397,7 @@ def main():
             local = time.perf_counter() - t0
             wall.append(max_over_ranks(local, dist, dev))
             wall_local.append(local)
+            last_stats[:] = [ret, length]
             if events:
                 kern.append(e0.elapsed_time(e1) / K)
             if not getattr(e, "auto_reset", False):
@@ -395,6 +424,12 @@ def main():
 
     repeats = max(1, args.repeats)
     wall, kern, survivors = timed_repeats(env, policy, fused, repeats, events=True)
+    if args.dump_outputs:
+        # (untimed; taken before the legs below step `env` again)
+        dump = {"episode_return": last_stats[0], "episode_length": last_stats[1].double(), "obs": env.obs, "state": env.get_state()}
+        if not fused:
+            dump.update(reward=env.reward, done=env.done)
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in dump.items()}, "_rank%d" % rank if world > 1 else "")
     elapsed = float(np.median(wall))
     kern_ms = float(np.median(kern))
     live_value = (world * float(np.median(live_steps)) / elapsed) if live_steps else None

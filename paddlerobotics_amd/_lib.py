@@ -41,6 +41,9 @@ def load():
         raise EtgError(
             "paddlerobotics_amd: %s is missing -- build it with `python -m paddlerobotics_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
+    # torch first: its HIP runtime then satisfies the library's libamdhip64.so.7 / libhsa-runtime64.so.1 by soname.  Loaded the
+    # other way round, the process maps a second HIP + HSA stack, and whichever initialises second finds no device.
+    import torch  # noqa: F401
     lib = C.CDLL(path)
     lib.etg_last_error.restype = C.c_char_p
     vp, i32 = C.c_void_p, C.c_int
