@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/etgsim.h (paddlerobotics_amd/csrc/libetgsim.so).
+"""ctypes binding of the C-ABI in include/etgsim.h and include/etgsim_step_policy.h (paddlerobotics_amd/csrc/libetgsim.so).
 
 There is no CPU fallback: if the library is missing this module raises, and if no HIP
 device is visible etg_create() fails with ETG_ERR_NO_DEVICE.
@@ -20,6 +20,8 @@ SYMBOLS = [
     "etg_prepare_next_dynamics", "etg_next_dynamics_pending",
     "etg_config_size", "etg_model_size", "etg_get_contact_impulses", "etg_set_contact_impulses", "etg_set_rollout_mode", "etg_rollout_wave_cycles", "etg_step_range",
 ]
+# entry points declared in a header of their own (same library, same ABI version): include/etgsim_step_policy.h
+STEP_POLICY_SYMBOLS = ["etg_step_policy"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 
@@ -81,6 +83,7 @@ def load():
     lib.etg_policy_destroy.argtypes = [vp]
     lib.etg_rollout_policy.argtypes = [vp, vp, i32, C.c_float, i32, i32, vp, vp, vp, vp]
     lib.etg_rollout_policy_record.argtypes = [vp, vp, i32, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.etg_step_policy.argtypes = [vp, vp, C.c_float, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_rollout_actions.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_prepare_next_dynamics.argtypes = [vp, vp, vp, vp]
     lib.etg_next_dynamics_pending.argtypes = [vp, vp, vp]

@@ -19,6 +19,7 @@
 
 #include "etg_core16.h"
 #include "policy_core.h"
+#include "../../include/etgsim_step_policy.h"
 
 // ---- translation units.  The device code of this file is ~120 instantiations of the physics tick: four minutes of
 // single-threaded code generation.  paddlerobotics_amd/build.py therefore compiles the file ETG_TU_PARTS times in parallel:
@@ -1088,10 +1089,37 @@ __global__ void __launch_bounds__(BLOCK) k_finish16(KCfg K, DevState D, const ui
   store_state16(c, D.base, D.leg, L);
 }
 
+// The restart of a robot whose step ended its episode, inside the step's launch (every robot has a cached settle): prepared
+// next-episode parameters installed (NX), cached settle -> registers, reset_finish (control state, episode accumulators, first
+// observation over the robot's row of `obs`; the pre-reset ring readings come from KCfg.cring), pending push cleared.  Called
+// by whole 16-lane rows (a robot's lanes together): step16_body<AUTO> and step_policy16_body<AUTO>.
+template <class Ctx>
+__device__ __forceinline__ void restart16(const Ctx& c, const KCfg& K, const DevState& D, const NextDyn& NX, State16<float>& L, float* obs) {
+  const int N = K.n_env;
+  if (NX.ok && NX.ok[c.env]) {   // parameters prepared for the next episode: install them (the cached settle below is theirs)
+    for (int k = c.sub; k < PR_DERIVED; k += 4) D.par[(size_t)k * c.NL + c.col] = NX.par[(size_t)k * c.NL + c.col];   // a leg's 4 lanes share its column
+    for (int k = c.r; k < ETG_DYN_DIM; k += 16) D.dyn[(size_t)c.env * ETG_DYN_DIM + k] = NX.dyn[(size_t)c.env * ETG_DYN_DIM + k];
+    __builtin_amdgcn_s_waitcnt(0);          // the row's reads of the flag and its stores are done before lane 0 clears it
+    __builtin_amdgcn_wave_barrier();
+    if (c.r == 0) NX.ok[c.env] = 0;
+    float stg2[kNStaged16];                 // the restart below reads the staged leg parameters: the new ones
+    stage16_issue(D, c, stg2);
+    stage16_commit(c, stg2);
+  }
+  L = load_state16<float>(c, D.cache_base, D.cache_leg);
+  L.p.x += D.reset_off[c.env] - D.cache_off[c.env];        // non-zero only on flat ground (settle_cached)
+  L.p.y += D.reset_off[N + c.env] - D.cache_off[N + c.env];
+  if (D.cache_off[(size_t)FIN_OK * N + c.env] > 0.5f) restart_from_cache16(c, K, L, D.ctl, D.ictl, D.legctl, D.cache_off, obs);
+  else reset_finish16(c, K, L, D.ring, D.ctl, D.ictl, D.legctl, D.etgp, obs);
+  if (c.r == 0) {
+    D.ictl[(size_t)IC_PUSH_LEFT * N + c.env] = 0;
+    for (int k = 0; k < 3; k++) D.ctl[(size_t)(CT_PUSH + k) * N + c.env] = 0.0f;
+  }
+}
+
 // env.step for the 4 robots of a wave.  AUTO (etg_step_autoreset while every robot has a cached settle): a robot whose step
-// ended its episode restarts inside the same launch -- cached settle -> registers, reset_finish (control state, episode
-// accumulators, first observation over the step's row; the pre-reset ring readings come from KCfg.cring), pending push
-// cleared.  reward / done / info stay the finished step's.
+// ended its episode restarts inside the same launch (restart16), its first observation over the step's row.  reward / done /
+// info stay the finished step's.
 template <bool FLAT, bool KNEE, bool PLAIN, bool AUTO>
 __device__ __forceinline__ void step16_body(const KCfg& K, const DevState& D, const float* action, const uint8_t* donef, float* obs,
                                             float* reward, uint8_t* done, float* info, float* lds_par, const NextDyn NX = NextDyn{nullptr, nullptr, nullptr}) {
@@ -1121,28 +1149,7 @@ __device__ __forceinline__ void step16_body(const KCfg& K, const DevState& D, co
 #endif
   control_step16_core(c, K, tp, L, S, D.ring, D.etgp, act, dflag, obs, r, d, info, hybrid ? hyb : nullptr);
   store_ctl16(c, K, S, D.ctl, D.ictl, D.legctl);
-  if (AUTO && d > 0.5f) {   // whole 16-lane rows take this branch together (d is the robot's)
-    const int N = K.n_env;
-    if (NX.ok && NX.ok[c.env]) {   // parameters prepared for the next episode: install them (the cached settle below is theirs)
-      for (int k = c.sub; k < PR_DERIVED; k += 4) D.par[(size_t)k * c.NL + c.col] = NX.par[(size_t)k * c.NL + c.col];   // a leg's 4 lanes share its column
-      for (int k = c.r; k < ETG_DYN_DIM; k += 16) D.dyn[(size_t)c.env * ETG_DYN_DIM + k] = NX.dyn[(size_t)c.env * ETG_DYN_DIM + k];
-      __builtin_amdgcn_s_waitcnt(0);          // the row's reads of the flag and its stores are done before lane 0 clears it
-      __builtin_amdgcn_wave_barrier();
-      if (c.r == 0) NX.ok[c.env] = 0;
-      float stg2[kNStaged16];                 // the restart below reads the staged leg parameters: the new ones
-      stage16_issue(D, c, stg2);
-      stage16_commit(c, stg2);
-    }
-    L = load_state16<float>(c, D.cache_base, D.cache_leg);
-    L.p.x += D.reset_off[c.env] - D.cache_off[c.env];        // non-zero only on flat ground (settle_cached)
-    L.p.y += D.reset_off[N + c.env] - D.cache_off[N + c.env];
-    if (D.cache_off[(size_t)FIN_OK * N + c.env] > 0.5f) restart_from_cache16(c, K, L, D.ctl, D.ictl, D.legctl, D.cache_off, obs);
-    else reset_finish16(c, K, L, D.ring, D.ctl, D.ictl, D.legctl, D.etgp, obs);
-    if (c.r == 0) {
-      D.ictl[(size_t)IC_PUSH_LEFT * N + c.env] = 0;
-      for (int k = 0; k < 3; k++) D.ctl[(size_t)(CT_PUSH + k) * N + c.env] = 0.0f;
-    }
-  }
+  if (AUTO && d > 0.5f) restart16(c, K, D, NX, L, obs);   // whole 16-lane rows take this branch together (d is the robot's)
   store_state16(c, D.base, D.leg, L);
 #ifdef ETG_PROFILE_PHASES
   if ((c.env & 3) == 0 && c.r == 0 && info) {   // every wave reports, in the info row of its first robot
@@ -1532,6 +1539,116 @@ __global__ void __launch_bounds__(BLOCK) k_rollout_policy16w_rec(KCfg K, DevStat
 }
 #undef ETG_POLICY16W_LDS
 
+// ---- etg_step_policy (include/etgsim_step_policy.h): ONE closed-loop control step of every robot, per wave as in
+// rollout_policy16w_body -- the actor on the wave's 4 observation rows (predict, or sample on the caller's noise: RecOut's
+// arithmetic), then the control step of those robots with its action, as step16_body.  The step's observation goes to
+// terminal_obs for every robot; AUTO: a robot whose step ended its episode restarts in the same launch (restart16) and its row
+// of `obs` becomes the reset observation.  No workgroup barrier (one wave per workgroup): the __syncthreads() are the LDS
+// hand-overs between the lanes of the wave.
+struct StepPolOut {
+  const float* noise;         // [N,12] N(0,1) draws of the stochastic actor, or NULL (predict)
+  const float4* w3s;          // the packed log-std head (k_pack_head) and its bias: read when noise != NULL
+  const float* b3s;
+  const uint8_t* donef;       // [N] forced episode ends, or NULL
+  float *act, *act_obs;       // [N,12] unscaled actions / [N,49] the rows the actor acted on: both optional
+  float *term_obs, *reward;   // [N,49] the step's observation of every robot, [N]
+  uint8_t* done;              // [N]
+  float* info;                // [N,64], or NULL
+};
+template <bool FLAT, bool KNEE, bool PLAIN, bool AUTO>
+__device__ __forceinline__ void step_policy16_body(const KCfg& K, const DevState& D, const PolicyW& P, float act_scale, float* obs,
+                                                   const StepPolOut& O, const NextDyn& NX, float* lds_par, float* obs4, float* abuf,
+                                                   float* hA, float* hB, float* part, float (*act4)[16]) {
+  using namespace pol;
+  const int lane = threadIdx.x;
+  const int blk = xcd_contiguous_block();             // 4 robots; the host guarantees N % 16 == 0 (the grid is N / 4 exactly)
+  const size_t row0 = (size_t)blk * 4;
+  // the actor: its rows, zero padded to WS columns, and (optionally) a copy of the rows for the replay memory
+  WaveRing ring;
+  wave_ring_start(ring, P.w1, lane);                  // the first k-groups of layer 1 arrive while the rows are staged
+  for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) obs4[idx] = obs[row0 * ETG_OBS_DIM + idx];
+  __syncthreads();
+  for (int idx = lane; idx < 4 * WS; idx += 64) {
+    const int r = idx / WS, col = idx - r * WS;
+    abuf[idx] = col < P.in_dim ? obs4[r * ETG_OBS_DIM + P.col0 + col] : 0.0f;
+  }
+  if (O.act_obs)
+    for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) O.act_obs[row0 * ETG_OBS_DIM + idx] = obs4[idx];
+  __syncthreads();
+  HeadW hw;
+  wave_hidden12(abuf, hA, hB, ring, P.w1, P.b1, P.b2, hw, P.w3, lane);
+  f32x4 mean = wave_head(hB, hw, part, lane);
+  f32x4 lstd = {0.f, 0.f, 0.f, 0.f};
+  if (O.noise) {
+    head_fetch(hw, O.w3s, lane);
+    lstd = wave_head(hB, hw, part, lane);
+  }
+  if (lane < ETG_ACT_DIM) {                           // lane = output neuron
+    const float b3 = P.b3[lane];
+    const float b3s = O.noise ? O.b3s[lane] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      float v = mean[i] + b3;
+      if (O.noise) {
+        const float ls = fminf(fmaxf(lstd[i] + b3s, -20.0f), 2.0f);
+        v = v + expf(ls) * O.noise[(row0 + i) * ETG_ACT_DIM + lane];
+      }
+      const float t = tanhf(v);
+      act4[i][lane] = t * act_scale;
+      if (O.act) O.act[(row0 + i) * ETG_ACT_DIM + lane] = t;   // the UNSCALED action (train.py:159)
+    }
+  }
+  __syncthreads();
+  // the control step (step16_body with the action from LDS and the observation rows in LDS: c.row_base)
+  GpuCtx16T<FLAT, KNEE, PLAIN> c;
+  make_ctx16_fields(K, D, c, lds_par, blk, lane);
+  float stg[kNStaged16];
+  stage16_issue(D, c, stg);
+  State16<float> L = load_state16<float>(c, D.base, D.leg);
+  StepCtl16<float> S = load_ctl16<float>(c, K, D.ctl, D.ictl, D.legctl);
+  TickPar<float> tp = load_tick_par<float>(c);
+  if (!PLAIN && K.ext_force) tp.fext = load_fext16<float>(c, D.ctl);
+  const float act = c.sub < 3 ? act4[lane >> 4][3 * c.leg + c.sub] : 0.0f;
+  const float dflag = O.donef ? (float)O.donef[c.env] : 0.0f;
+  stage16_commit(c, stg);
+  c.row_base = (int)row0;                             // observation rows: obs4; info rows: through a pointer moved by the same rows
+  float r, d;
+  control_step16_core(c, K, tp, L, S, D.ring, D.etgp, act, dflag, obs4, r, d, O.info ? O.info + row0 * ETG_INFO_DIM : (float*)nullptr);
+  store_ctl16(c, K, S, D.ctl, D.ictl, D.legctl);
+  __syncthreads();
+  for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) O.term_obs[row0 * ETG_OBS_DIM + idx] = obs4[idx];
+  if (AUTO) {
+    __syncthreads();                                  // the rows are read before a restart writes its reset row over them
+    if (d > 0.5f) restart16(c, K, D, NX, L, obs4);    // whole 16-lane rows take this branch together (d is the robot's)
+  }
+  store_state16(c, D.base, D.leg, L);
+  if (c.r == 0) {
+    O.reward[c.env] = r;
+    O.done[c.env] = d > 0.5f ? 1 : 0;
+  }
+  __syncthreads();
+  for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) obs[row0 * ETG_OBS_DIM + idx] = obs4[idx];
+}
+#define ETG_STEP_POLICY16_LDS                                                                \
+  __shared__ float lds_par[LDS16_FIELDS * BLOCK];                                            \
+  __shared__ __attribute__((aligned(16))) float obs4[4 * ETG_OBS_DIM];                       \
+  __shared__ __attribute__((aligned(16))) float abuf[4 * pol::WS];                           \
+  __shared__ __attribute__((aligned(16))) float hA[4 * pol::HS];                             \
+  __shared__ __attribute__((aligned(16))) float hB[4 * pol::HS];                             \
+  __shared__ __attribute__((aligned(16))) float part[64 * 4];                                \
+  __shared__ float act4[4][16];
+template <bool FLAT, bool KNEE, bool PLAIN>
+__global__ void __launch_bounds__(BLOCK) k_step_policy16(KCfg K, DevState D, PolicyW P, float act_scale, float* obs, StepPolOut O) {
+  ETG_STEP_POLICY16_LDS
+  step_policy16_body<FLAT, KNEE, PLAIN, false>(K, D, P, act_scale, obs, O, NextDyn{nullptr, nullptr, nullptr}, lds_par, obs4, abuf, hA, hB, part, act4);
+}
+template <bool FLAT, bool KNEE, bool PLAIN>
+__global__ void __launch_bounds__(BLOCK) k_step_policy16_ar(KCfg K, DevState D, PolicyW P, float act_scale, float* obs, StepPolOut O, NextDyn NX) {
+  ETG_STEP_POLICY16_LDS
+  step_policy16_body<FLAT, KNEE, PLAIN, true>(K, D, P, act_scale, obs, O, NX, lds_par, obs4, abuf, hA, hB, part, act4);
+}
+#undef ETG_STEP_POLICY16_LDS
+
 // Closed loop on the 4-lanes-per-robot mapping (the mapping of every batch above 4096 robots): a workgroup of 4 waves owns
 // 64 robots (16 per wave, one leg per lane).  The policy runs over TWO stacked 16-row tiles at a time (hidden_layer_rt): every
 // weight fragment fetched from L2 feeds two MFMAs, so the weight delivery per robot is half that of k_rollout_policy16, and a
@@ -1810,6 +1927,8 @@ __global__ void k_extra_sensors(KCfg K, ModelF M, DevState D, const float* obs, 
 #define ETG_ARGS_TAPE KCfg, DevState, int, const float*, float*, TapeOut
 #define ETG_ARGS_POLICY KCfg, DevState, PolicyW, int, float, float*
 #define ETG_ARGS_POLICY_REC KCfg, DevState, PolicyW, int, float, float*, RecOut
+#define ETG_ARGS_STEP_POLICY KCfg, DevState, PolicyW, float, float*, StepPolOut
+#define ETG_ARGS_STEP_POLICY_AR KCfg, DevState, PolicyW, float, float*, StepPolOut, NextDyn
 #if ETG_TU_PARTS > 1
 #define ETG_SLOT_OWNER(S) (1 + ((S) - 1) % (ETG_TU_PARTS - 1))
 #if ETG_SLOT_OWNER(1) == ETG_TU_PART
@@ -1889,6 +2008,8 @@ ETG_INST16(k_rollout16, 4, 5, 6, 7, 1, 2, ETG_ARGS_ROLLOUT)
 ETG_INST16(k_rollout_actions16, 3, 4, 5, 6, 7, 1, ETG_ARGS_TAPE)
 ETG_INST16(k_rollout_policy16w, 2, 4, 6, 1, 3, 5, ETG_ARGS_POLICY)
 ETG_INST16(k_rollout_policy16w_rec, 7, 2, 4, 6, 1, 3, ETG_ARGS_POLICY_REC)
+ETG_INST16(k_step_policy16, 3, 5, 7, 2, 4, 6, ETG_ARGS_STEP_POLICY)
+ETG_INST16(k_step_policy16_ar, 6, 1, 3, 5, 7, 2, ETG_ARGS_STEP_POLICY_AR)
 ETG_INSTP16(k_rollout_policy16, false, 2, 3, 4, 5, 6, 7, ETG_ARGS_POLICY)
 ETG_INSTP16(k_rollout_policy16, true, 1, 2, 3, 4, 5, 6, ETG_ARGS_POLICY)
 ETG_INSTP16(k_rollout_policy16_rec, false, 7, 1, 2, 3, 4, 5, ETG_ARGS_POLICY_REC)
@@ -2678,6 +2799,46 @@ extern "C" int etg_rollout_policy_record(EtgHandle* h, EtgPolicy* pol, int n_ste
   }
   HIP_TRY(hipGetLastError());
   if (ret || len) return etg_episode_stats(h, ret, len, stream);
+  return ETG_OK;
+}
+
+// One closed-loop control step of every robot (include/etgsim_step_policy.h): k_step_policy16 / k_step_policy16_ar, one launch
+// (auto_reset without a cached settle for every robot: the step launch, then etg_reset masked by `done`, as etg_step_autoreset)
+extern "C" int etg_step_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int auto_reset,
+                               const float* noise, const uint8_t* donef, float* obs, float* act, float* act_obs, float* terminal_obs,
+                               float* reward, uint8_t* done, float* info, void* stream) {
+  CHECK_HANDLE(h);
+  if (!pol || !obs || !terminal_obs || !reward || !done)
+    return fail(ETG_ERR_BAD_ARG, "etg_step_policy: policy, obs, terminal_obs, reward and done must be non-null");
+  if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_step_policy: call etg_reset first");
+  if (noise && !pol->has_std) return fail(ETG_ERR_STATE, "etg_step_policy: sampling needs etg_policy_load_std() first");
+  if (pol->device != h->device) return fail(ETG_ERR_BAD_ARG, "etg_step_policy: policy and simulator live on different devices");
+  if (obs_col0 < 0 || obs_col0 + pol->in_dim > ETG_OBS_DIM || pol->out_dim != ETG_ACT_DIM)
+    return fail(ETG_ERR_BAD_ARG, "etg_step_policy: the policy must map observation columns [col0, col0 + in_dim) to 12 actions");
+  if (precision != 0 || pol->in_dim > 4 * pol::KQ1)
+    return fail(ETG_ERR_BAD_ARG, "etg_step_policy: the kernel runs the fp32 per-wave actor tile: precision 0, in_dim <= 64");
+  if (h->lanes != 16 || h->N % 16 != 0)
+    return fail(ETG_ERR_BAD_ARG, "etg_step_policy: needs the 16-lanes-per-robot mapping and num_envs % 16 == 0");
+  if (h->K.motor_mode == 2) return fail(ETG_ERR_BAD_ARG, "etg_step_policy: the HYBRID motor mode is not covered (its action has 60 columns)");
+  if (h->K.noise_on) return fail(ETG_ERR_BAD_ARG, "etg_step_policy: sensor noise is not covered: switch it off or step");
+  if (auto_reset) refresh_all_cached(h);
+  const bool fused_reset = auto_reset && h->all_cached;
+  advance_obs_stream(h, fused_reset ? 2 : 1);
+  const PolicyW Pq = {(const float4*)pol->w12q, nullptr, (const float4*)pol->w3q, pol->b1, pol->b2, pol->b3, pol->in_dim, pol->out_dim, obs_col0};
+  const StepPolOut O = {noise, (const float4*)pol->w3sq, pol->b3s, donef, act, act_obs, terminal_obs, reward, done, info};
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g(h->N / 4);
+  if (fused_reset) {
+    LAUNCH16(k_step_policy16_ar, g, s, h->K, h->D, Pq, act_scale, obs, O, h->NX);
+  } else {
+    LAUNCH16(k_step_policy16, g, s, h->K, h->D, Pq, act_scale, obs, O);
+  }
+  HIP_TRY(hipGetLastError());
+  if (auto_reset && !fused_reset) {   // some robot needs a simulated settle: the general reset path masked by the done bytes
+    if (h->push_on)
+      if (int rc = etg_clear_pushes(h, done, stream)) return rc;
+    return etg_reset(h, done, obs, stream);
+  }
   return ETG_OK;
 }
 

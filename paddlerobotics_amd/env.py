@@ -678,21 +678,26 @@ class BatchedQuadrupedEnv:
         for st in streams:
             cur.wait_stream(st)
 
+    def _donef_bytes(self, donef):
+        """step()'s donef argument as the uint8 [N] device tensor the library reads, or None"""
+        if donef is None:
+            return None
+        if isinstance(donef, (bool, int, np.bool_)):
+            if not bool(donef):                               # False is the same as no donef at all
+                return None
+            if self._all_done is None:
+                self._all_done = torch.ones(self.num_envs, dtype=torch.uint8, device=self.device)
+            return self._all_done
+        df = torch.as_tensor(donef, device=self.device).to(torch.uint8).contiguous()
+        if tuple(df.shape) != (self.num_envs,):
+            raise ValueError("donef must be a bool or have shape [N]")
+        return df
+
     def step(self, action, donef=None, want_info=True, groups=1):
         """One control step of every robot (env.step of the reference, batched).  groups=G > 1: the batch is stepped as G
         sub-batches on G streams (identical results); see rollout_policy(fused=False, groups=G) for the loop that gains from it."""
         a = None if action is None else self._f32(action, (self.num_envs, self.action_space.shape[0]), "action")   # NULL = zero residual
-        df = None
-        if donef is not None:
-            if isinstance(donef, (bool, int, np.bool_)):
-                if bool(donef):                               # False is the same as no donef at all
-                    if self._all_done is None:
-                        self._all_done = torch.ones(self.num_envs, dtype=torch.uint8, device=self.device)
-                    df = self._all_done
-            else:
-                df = torch.as_tensor(donef, device=self.device).to(torch.uint8).contiguous()
-                if tuple(df.shape) != (self.num_envs,):
-                    raise ValueError("donef must be a bool or have shape [N]")
+        df = self._donef_bytes(donef)
         if self._rand_force:
             self._random_pushes()
         # auto_reset: robots whose episode just ended start the next one inside the same call (settle cache -> state, control
@@ -726,6 +731,81 @@ class BatchedQuadrupedEnv:
         else:
             self._last_view = self._obs_view()
         return (self._last_view, self.reward, self.done.view(torch.bool) if want_info else self.done, info)
+
+    def _step_policy_refusal(self, policy, precision):
+        """why step_policy's kernel does not cover this env / policy (None: it does)"""
+        contiguous = self._cols == list(range(self._cols[0], self._cols[0] + len(self._cols)))
+        if self.lanes_per_robot != 16:
+            return "the 4-lanes-per-robot mapping is not covered (lanes_per_robot=16, at most 4096 robots by default)"
+        if self.num_envs % 16 != 0:
+            return "num_envs must be a multiple of 16"
+        if self.motor_mode == 2:
+            return "the HYBRID motor mode is not covered"
+        if self._hist_T > 0:
+            return "observation history (sensor_mode['RNN']) is not covered"
+        if self._xcols:
+            return "extra sensor columns are not covered"
+        if getattr(self, "_noise_on", False):
+            return "sensor noise is not covered"
+        if self._rand_force:
+            return "random pushes are not covered"
+        if not contiguous or policy.obs_dim != len(self._cols) or policy.action_dim != A.NUM_MOTORS:
+            return "the policy must map the env's (contiguous) observation columns to 12 actions"
+        if int(precision) != 0:
+            return "precision must be 0 (the fp32 actor)"
+        return None
+
+    def step_policy(self, policy, act_scale=0.3, mode="predict", noise=None, donef=None, want_info=True, precision=0, generator=None):
+        """One closed-loop control step of every robot in ONE launch (include/etgsim_step_policy.h): the actor on the current
+        observation -- mode "predict": tanh(mean); "sample": tanh(mean + exp(clamp(log_std, -20, 2)) * noise) with noise [N,12]
+        ~ N(0,1), drawn from `generator` when not given (alg/sac.py:60-76) -- then step() with action * act_scale.  On an
+        auto_reset env finished robots restart inside the same launch, as in step(); with random_dynamics they restart on the
+        prepared rows of their next episode (random_dynamics_refresh > 1), or -- where the library cannot prepare them -- through
+        the masked reset() after the launch that step() takes then too.
+
+        Returns (obs, reward, done, info, action): action [N,12] is the UNSCALED action (what the replay memory stores,
+        train.py:159); info["terminal_obs"] is the observation the step produced for every robot, before any restart (the
+        next_obs of the transition), info["acted_obs"] the observation the actor acted on, and on an auto_reset env
+        info["reset"] marks the restarted robots.  These three are present with want_info=False too.  The returned tensors
+        are the env's buffers: the next call writes over them.  FusedKernelUnavailable: the configuration is outside the kernel
+        (4-lane mapping, num_envs % 16 != 0, HYBRID mode, observation history, extra sensors, sensor noise, random pushes)."""
+        if mode not in ("predict", "sample"):
+            raise ValueError("mode must be 'predict' or 'sample'")
+        why = self._step_policy_refusal(policy, precision)
+        if why:
+            raise FusedKernelUnavailable("step_policy: " + why)
+        N = self.num_envs
+        if mode == "sample":
+            if noise is None:
+                noise = torch.randn(N, A.NUM_MOTORS, device=self.device, generator=generator)
+            noise = self._f32(noise, (N, A.NUM_MOTORS), "noise")
+        elif noise is not None:
+            raise ValueError("noise is for mode='sample'")
+        df = self._donef_bytes(donef)
+        if getattr(self, "_sp_buf", None) is None:
+            z = lambda *shape: torch.zeros(*shape, device=self.device)
+            self._sp_buf = (z(N, A.NUM_MOTORS), z(N, A.OBS_DIM), z(N, A.OBS_DIM))
+        act, act_obs, term = self._sp_buf
+        fused_reset = self.auto_reset and (not self._rand_dyn or self._nx_on)   # as in step()
+        _lib.check(self._lib.etg_step_policy(self._h, policy._h, C.c_float(act_scale), int(precision), int(self._cols[0]),
+                                             int(fused_reset), _ptr(noise), _ptr(df), _ptr(self.obs), _ptr(act), _ptr(act_obs),
+                                             _ptr(term), _ptr(self.reward), _ptr(self.done),
+                                             _ptr(self.info_buf) if want_info else None, self._stream()))
+        self._keep_step = (noise, df)
+        info = self._info() if want_info else {}
+        sel = (lambda o: o) if self._col_idx is None else (lambda o: o.index_select(1, self._col_idx))
+        info["terminal_obs"] = sel(term)
+        info["acted_obs"] = sel(act_obs)
+        if self.auto_reset:
+            info["reset"] = self.done.view(torch.bool)
+        if self.auto_reset and not fused_reset:   # random_dynamics without prepared rows: new draws through the masked reset
+            self._reset_mask = self.done.clone()
+            self.reset(env_ids=self._reset_mask, _keep_offsets=True)
+        else:
+            self._last_view = self._obs_view()
+        if self._nx_on:
+            self._refresh_next_dynamics()
+        return (self._last_view, self.reward, self.done.view(torch.bool) if want_info else self.done, info, act)
 
     def set_rollout_mode(self, simulate_finished=False):
         """The fused rollouts (rollout_openloop / _policy / _policy_record / _actions) stop simulating a robot when its episode

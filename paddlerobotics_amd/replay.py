@@ -9,7 +9,8 @@
 One env here is thousands of robots, so one `step()` yields a BATCH of transitions: `append_batch` writes the rows of the
 robots whose episode is still running into a ring of transitions that lives in HBM next to the simulator -- no host copy,
 no host synchronisation (the write position is a device scalar; rows of finished robots go to a scratch slot).
-`collect_transitions` is the batched run_train_episode / run_EStrain_episode collection loop.
+`collect_transitions` is the batched run_train_episode / run_EStrain_episode collection loop; `collect_continuous` is the
+continuous form of run_train_episode's collection on an auto_reset env (one env.step_policy launch per control step).
 
 On a HIP device the appends go through etg_replay_begin / etg_replay_end (csrc/etg_replay.hip: prefix sum over the alive
 bytes + scattered rows, three launches per control step, the info sums and the alive update folded in); the torch
@@ -298,6 +299,55 @@ def collect_transitions(env, rpm, max_step, policy=None, action_bound=0.3, mode=
     ret, ln = env.episode_stats()
     infos["success_rate"] = success / ln.to(torch.float32).clamp(min=1)
     return ret, ln, infos
+
+
+def collect_continuous(env, rpm, n_steps, policy, action_bound=0.3, mode="sample", noise=None, generator=None, donef=None):
+    """Continuous collection for SAC (run_train_episode, train.py:129-179, batched without episode boundaries): n_steps control
+    steps of every robot of an auto_reset env through env.step_policy (actor + step + restart in one launch), every step's N
+    transitions appended to `rpm`:
+
+      obs = the row the actor acted on, action = the unscaled action, reward,
+      next_obs = the step's observation before any restart (info["terminal_obs"]),
+      terminal = bootstrap_mask(done, the robot's OWN episode step): 1 - done, 1 from episode step 2000 on (train.py:148-149)
+
+    Robots do not wait for each other: a finished robot restarts in the same launch, and the next call continues every robot's
+    episode where this one stopped (the running returns and step counts are read from the simulator at the start).  No host
+    synchronisation.  mode: "sample" (agent.sample; noise [n_steps, N, 12] ~ N(0,1) may be given, else drawn from `generator`)
+    or "predict".  donef [n_steps, N] (bool / uint8, optional): forced episode ends per step, e.g. a time limit (train.py:145
+    `donef=(steps > max_step)`).  Returns (ret [N], len [N]): return and length of the LAST episode of each robot that ended
+    during the call (len 0: none of its episodes ended)."""
+    if not env.auto_reset:
+        raise ValueError("collect_continuous needs an env made with auto_reset=True")
+    if mode not in ("predict", "sample"):
+        raise ValueError("mode must be 'predict' or 'sample'")
+    n, dev, T = env.num_envs, env.device, int(n_steps)
+    if noise is not None:
+        if mode != "sample":
+            raise ValueError("noise is for mode='sample'")
+        noise = torch.as_tensor(noise, dtype=torch.float32, device=dev)
+        if tuple(noise.shape) != (T, n, 12):
+            raise ValueError("noise must be [n_steps, num_envs, 12]")
+    if donef is not None:
+        donef = torch.as_tensor(donef, device=dev).to(torch.uint8).contiguous()
+        if tuple(donef.shape) != (T, n):
+            raise ValueError("donef must be [n_steps, num_envs]")
+    run_ret, run_len = env.episode_stats()        # the episodes running now: this call continues them
+    last_ret = torch.zeros(n, device=dev)
+    last_len = torch.zeros(n, dtype=torch.int32, device=dev)
+    for k in range(T):
+        _, reward, done, info, action = env.step_policy(policy, action_bound, mode, noise=None if noise is None else noise[k],
+                                                        donef=None if donef is None else donef[k], want_info=False,
+                                                        generator=generator)
+        d = done.view(-1).to(torch.bool)
+        run_ret = run_ret + reward
+        run_len = run_len + 1                       # the 1-based episode step of this transition, per robot
+        terminal = torch.where(run_len >= BOOTSTRAP_ALWAYS_FROM, torch.ones_like(reward), 1.0 - d.to(torch.float32))
+        rpm.append_batch(info["acted_obs"], action, reward, info["terminal_obs"], terminal)
+        last_ret = torch.where(d, run_ret, last_ret)
+        last_len = torch.where(d, run_len, last_len)
+        run_ret = torch.where(d, torch.zeros_like(run_ret), run_ret)
+        run_len = torch.where(d, torch.zeros_like(run_len), run_len)
+    return last_ret, last_len
 
 
 def obs2noise(obs, generator=None):
