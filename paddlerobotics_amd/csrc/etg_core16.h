@@ -283,30 +283,28 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
                     zero, I.h.z, -I.h.y, I.m,
                     -I.h.z, zero, I.h.x, zero, I.m,
                     I.h.y, -I.h.x, zero, zero, zero, I.m};
-  F s[21];
+  // sr[0..20]: the Schur entries, sr[21..26]: the base right-hand side -- the 27 row sums advance stage by stage in ONE
+  // reduction (per-entry butterflies, the same arithmetic as c.sum16 entry by entry: every lane gets the same bits).
+  // (Written as 21 separate c.sum16 chains plus a c.sum16x6, the scheduler serialised them on flat ground too -- 4 dependent
+  // DPP adds with an s_nop between each -- and the separate right-hand side stood behind the Schur sums.)
+  F sr[27];
 #pragma unroll
   for (int i = 0; i < 6; i++)
 #pragma unroll
-    for (int j = 0; j <= i; j++) s[i * (i + 1) / 2 + j] = lm[i * (i + 1) / 2 + j] - comp(P, i) * comp(Fs, j);
-  // Same arithmetic either way (per-entry butterflies).  On flat ground the scheduler interleaves the 21 chains by
-  // itself and shaves 16 instructions off the explicit form; in the heightfield kernels (more registers live) it
-  // serialises them -- 4 dependent DPP adds with an s_nop 1 between each -- unless they are written stage by stage.
-  if (Ctx::kFlat) {
+    for (int j = 0; j <= i; j++) sr[i * (i + 1) / 2 + j] = lm[i * (i + 1) / 2 + j] - comp(P, i) * comp(Fs, j);
 #pragma unroll
-    for (int i = 0; i < 21; i++) s[i] = c.sum16(s[i]);
-  } else {
-    c.sum16xn(s, 21);
-  }
+  for (int i = 0; i < 6; i++) sr[21 + i] = comp(f, i) + rl * comp(P, i);
+  c.sum16xn(sr, 27);
+  F s[21];
+#pragma unroll
+  for (int i = 0; i < 21; i++) s[i] = sr[i];
   s[0] = s[0] + I0s.xx;
   s[1] = s[1] + I0s.xy; s[2] = s[2] + I0s.yy;
   s[3] = s[3] + I0s.xz; s[4] = s[4] + I0s.yz; s[5] = s[5] + I0s.zz;
   s[9] = s[9] + m0; s[14] = s[14] + m0; s[20] = s[20] + m0;
   F rb[6];
 #pragma unroll
-  for (int i = 0; i < 6; i++) rb[i] = comp(f, i) + rl * comp(P, i);
-  c.sum16x6(rb);
-#pragma unroll
-  for (int i = 0; i < 6; i++) rb[i] = -comp(fb0, i) - rb[i];
+  for (int i = 0; i < 6; i++) rb[i] = -comp(fb0, i) - sr[21 + i];
   if (!Ctx::kPlain) {  // external force on the trunk COM (world frame; zero unless set) -> base frame: R^T f
     rb[3] = rb[3] + Rw.r0.x * tp.fext.x + Rw.r1.x * tp.fext.y + Rw.r2.x * tp.fext.z;
     rb[4] = rb[4] + Rw.r0.y * tp.fext.x + Rw.r1.y * tp.fext.y + Rw.r2.y * tp.fext.z;

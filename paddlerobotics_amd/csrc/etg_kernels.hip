@@ -923,8 +923,13 @@ struct GpuCtx16 {
   __device__ __forceinline__ void st_row_leg(float* p, int rowlen, int col0, float v) const { if (gate && sub == 0) p[(size_t)(env - row_base) * rowlen + col0 + leg] = v; }
   __device__ __forceinline__ void st_row_env(float* p, int rowlen, int c_, float v) const { if (gate && r == 0) p[(size_t)(env - row_base) * rowlen + c_] = v; }
   __device__ __forceinline__ float ld_row_env(const float* p, int rowlen, int c_) const { return p[(size_t)(env - row_base) * rowlen + c_]; }
+  // phase boundary of the 16-lane tick: no scheduling barrier in the product build.  A barrier here makes the tail of one
+  // phase's dependent chain (the LDL^T solve, a DPP reduction) sit out its latency before the next phase may start; without
+  // it the scheduler overlaps the two, registers and scratch stay where they were, and the headline rollout runs 3-6 %
+  // faster (profiles/r07_ab_experiments.txt section 5).  -DETG_PHASE_BARRIER16 restores the barriers for A/B builds; the
+  // profiling build keeps them around its s_memtime stamps so that every stamp closes exactly its own phase.
   __device__ __forceinline__ void phase([[maybe_unused]] int id) const {
-#ifndef ETG_NO_PHASE_BARRIER16
+#if defined(ETG_PHASE_BARRIER16) || defined(ETG_PROFILE_PHASES)
     __builtin_amdgcn_sched_barrier(0);
 #endif
 #ifdef ETG_PROFILE_PHASES
