@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI in include/etgsim.h and include/etgsim_step_policy.h (paddlerobotics_amd/csrc/libetgsim.so).
+"""ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h and include/etgsim_terminal.h
+(paddlerobotics_amd/csrc/libetgsim.so).
 
 There is no CPU fallback: if the library is missing this module raises, and if no HIP
 device is visible etg_create() fails with ETG_ERR_NO_DEVICE.
@@ -22,6 +23,8 @@ SYMBOLS = [
 ]
 # entry points declared in a header of their own (same library, same ABI version): include/etgsim_step_policy.h
 STEP_POLICY_SYMBOLS = ["etg_step_policy"]
+# ... and include/etgsim_terminal.h
+TERMINAL_SYMBOLS = ["etg_step_autoreset_terminal", "etg_extra_sensors_terminal"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 
@@ -84,6 +87,8 @@ def load():
     lib.etg_rollout_policy.argtypes = [vp, vp, i32, C.c_float, i32, i32, vp, vp, vp, vp]
     lib.etg_rollout_policy_record.argtypes = [vp, vp, i32, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_step_policy.argtypes = [vp, vp, C.c_float, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.etg_step_autoreset_terminal.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.etg_extra_sensors_terminal.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.etg_rollout_actions.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_prepare_next_dynamics.argtypes = [vp, vp, vp, vp]
     lib.etg_next_dynamics_pending.argtypes = [vp, vp, vp]

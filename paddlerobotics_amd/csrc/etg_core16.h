@@ -1213,8 +1213,10 @@ ETG_HD void control_step16_core(const Ctx& c, const KCfg& K, TickPar<F>& tp, Sta
                                 float* rec_q = nullptr,     // action-tape rollouts: rows [N,12] / [N,6] receiving info["joint_angle"] and
                                 float* rec_imu = nullptr,   // info["obs-IMU"] of this step (Dynamic_parallel_model.py:63-64)
                                 bool skip_dead = false,     // fused rollouts under KCfg.stop_at_done: see below
-                                float* obs_end = nullptr) { // skip_dead: a second row buffer that receives the LAST row of a robot whose episode
+                                float* obs_end = nullptr,   // skip_dead: a second row buffer that receives the LAST row of a robot whose episode
                                                             // ends in this step (tape rollouts: `obs` is the tape's row of the step then)
+                                float* obs_term = nullptr) {// auto-reset steps: a second row buffer that receives every robot's row (the
+                                                            // terminal observation, kept when a restart writes its reset row over `obs`)
   const F mj = c.jointf();
   // An ended episode is not simulated any more (skip_dead; the reference's loops leave at `done`: pretrain.py:137-153,
   // train.py:226-247).  SIMD lanes cannot sit a step out, so a finished robot (S.alive == 0) is taken out of everything that
@@ -1315,6 +1317,7 @@ ETG_HD void control_step16_core(const Ctx& c, const KCfg& K, TickPar<F>& tp, Sta
   if (want_obs || info || ending) {
     const Delayed16<F> D = ring_read16<F>(c, K, ring, tick);
     write_obs16(c, K, L, D, S.r0, S.r1, S.r2, etg, lbx, lby, lbz, obs, imu);
+    if (obs_term) write_obs16(c, K, L, D, S.r0, S.r1, S.r2, etg, lbx, lby, lbz, obs_term, imu);
     if (ending && obs_end && obs_end != obs) {
       c.set_gate(is_live && (done > F(0.5f)));
       write_obs16(c, K, L, D, S.r0, S.r1, S.r2, etg, lbx, lby, lbz, obs_end, imu);

@@ -20,6 +20,7 @@
 #include "etg_core16.h"
 #include "policy_core.h"
 #include "../../include/etgsim_step_policy.h"
+#include "../../include/etgsim_terminal.h"
 
 // ---- translation units.  The device code of this file is ~120 instantiations of the physics tick: four minutes of
 // single-threaded code generation.  paddlerobotics_amd/build.py therefore compiles the file ETG_TU_PARTS times in parallel:
@@ -163,6 +164,21 @@ constexpr int BLOCK = 64;
 // pending flag per robot.  The settle that belongs to them already sits in the robot's settle cache; the restart inside
 // etg_step_autoreset (or the next etg_reset of the robot) installs the rows.  All null when the feature is unused.
 struct NextDyn { float* par; float* dyn; unsigned char* ok; };
+// What an in-launch restart overwrites, kept by the AR step kernels for etg_step_autoreset_terminal (include/etgsim_terminal.h):
+// the step's observation row of every robot (written from the values that produce it: next to the row of `obs` on 16 lanes,
+// instead of it on 4 -- step4_body), and for each
+// restarted robot the pre-restart values its extra sensor columns read (term_ctx_store).  Both null from etg_step_autoreset.
+struct TermOut { float* obs; float* ctx; };
+// the terminal_ctx row of a robot whose restart follows (lane `lane` of the robot's `lanes`): the episode step index of its
+// terminal row (IC_STEP after the step), the step's trunk force (set + push: the restart clears the push) and its dynamic_param
+// row (a restart on prepared next-episode rows replaces it).  Called before the restart touches any of them.
+__device__ __forceinline__ void term_ctx_store(const KCfg& K, const DevState& D, int env, int lane, int lanes, int step, float* ctx) {
+  const int N = K.n_env;
+  float* row = ctx + (size_t)env * ETG_TERM_CTX_DIM;
+  if (lane == 0) row[ETG_TERM_STEP] = (float)step;
+  if (lane < 3) row[ETG_TERM_FORCE + lane] = D.ctl[(size_t)(CT_FEXT + lane) * N + env] + D.ctl[(size_t)(CT_PUSH + lane) * N + env];
+  for (int k = lane; k < ETG_DYN_DIM; k += lanes) row[ETG_TERM_DYN + k] = D.dyn[(size_t)env * ETG_DYN_DIM + k];
+}
 // install the pending rows of the masked robots (a reset of theirs is about to use the settle cache that belongs to the rows)
 #if ETG_TU_HOST   // small kernels: compiled with the host side only (part 0)
 __global__ void __launch_bounds__(256) k_next_take(KCfg K, DevState D, NextDyn NX, const uint8_t* mask) {
@@ -398,10 +414,14 @@ __device__ __forceinline__ void restart_from_cache4(const Ctx& c, const KCfg& K,
   for (int k = c.lane; k < ETG_OBS_DIM; k += 4) obs[(size_t)c.env * ETG_OBS_DIM + k] = fin[(size_t)(FIN_OBS + k) * N + c.env];
 }
 
-// env.step for the 16 robots of a wave (one quad each); AUTO: see step16_body
+// env.step for the 16 robots of a wave (one quad each); AUTO: see step16_body.  T (AUTO only): the step's row of every robot
+// goes to T.obs INSTEAD of `obs` -- the 4-lane tick sits at the 512-register budget, and a second set of row stores costs it
+// scratch -- so a robot that goes on has its row of `obs` from T.obs after the launch (etg_step_autoreset_terminal: k_term_rows);
+// a restarted robot's reset row goes to `obs` as without T.
 template <bool FLAT, bool PLAIN, bool AUTO, int BODY = 0>
 __device__ __forceinline__ void step4_body(const KCfg& K, const DevState& D, const float* action, const uint8_t* donef, float* obs,
-                                           float* reward, uint8_t* done, float* info, float* lds_par, const NextDyn NX = NextDyn{nullptr, nullptr, nullptr}) {
+                                           float* reward, uint8_t* done, float* info, float* lds_par, const NextDyn NX = NextDyn{nullptr, nullptr, nullptr},
+                                           const TermOut T = TermOut{nullptr, nullptr}) {
   GpuCtxT<FLAT, PLAIN, BODY> c;
   if (!make_ctx(K, c)) return;
   // every cold load of the launch head is requested before the first wait (see step16_body)
@@ -429,10 +449,11 @@ __device__ __forceinline__ void step4_body(const KCfg& K, const DevState& D, con
   c.prof_last = clock64();
   long long t_begin = c.prof_last;
 #endif
-  control_step_core(c, K, tp, fext, L, S, D.ring, D.etgp, act, dflag, obs, r, d, info, hybrid ? hyb : nullptr);
+  control_step_core(c, K, tp, fext, L, S, D.ring, D.etgp, act, dflag, AUTO && T.obs ? T.obs : obs, r, d, info, hybrid ? hyb : nullptr);
   store_ctl4(c, K, S, D.ctl, D.ictl, D.legctl);
   if (AUTO && d > 0.5f) {   // whole quads take this branch together
     const int N = K.n_env;
+    if (T.ctx) term_ctx_store(K, D, c.env, c.lane, 4, S.step_count, T.ctx);
     if (NX.ok && NX.ok[c.env]) {   // parameters prepared for the next episode: install them (the cached settle below is theirs)
       for (int k = 0; k < PR_DERIVED; k++) D.par[(size_t)k * c.NL + c.gid] = NX.par[(size_t)k * c.NL + c.gid];
       for (int k = c.lane; k < ETG_DYN_DIM; k += 4) D.dyn[(size_t)c.env * ETG_DYN_DIM + k] = NX.dyn[(size_t)c.env * ETG_DYN_DIM + k];
@@ -471,9 +492,9 @@ __global__ void __launch_bounds__(BLOCK) k_step(KCfg K, DevState D, const float*
 }
 template <bool FLAT, bool PLAIN, int BODY = 0>
 __global__ void __launch_bounds__(BLOCK) k_step_ar(KCfg K, DevState D, const float* action, const uint8_t* donef, float* obs,
-                                                    float* reward, uint8_t* done, float* info, NextDyn NX) {
+                                                    float* reward, uint8_t* done, float* info, NextDyn NX, TermOut T) {
   __shared__ float lds_par[PR_N * BLOCK];
-  step4_body<FLAT, PLAIN, true, BODY>(K, D, action, donef, obs, reward, done, info, lds_par, NX);
+  step4_body<FLAT, PLAIN, true, BODY>(K, D, action, donef, obs, reward, done, info, lds_par, NX, T);
 }
 
 // episode returns / lengths [N] for the caller, or nulls; cyc: one slot per wavefront of the launch receiving the shader-clock
@@ -1124,10 +1145,12 @@ __device__ __forceinline__ void restart16(const Ctx& c, const KCfg& K, const Dev
 
 // env.step for the 4 robots of a wave.  AUTO (etg_step_autoreset while every robot has a cached settle): a robot whose step
 // ended its episode restarts inside the same launch (restart16), its first observation over the step's row.  reward / done /
-// info stay the finished step's.
+// info stay the finished step's.  T (AUTO only, etg_step_autoreset_terminal): the step's row of every robot also goes to T.obs,
+// and a restarting robot's pre-restart sensor context to T.ctx.
 template <bool FLAT, bool KNEE, bool PLAIN, bool AUTO>
 __device__ __forceinline__ void step16_body(const KCfg& K, const DevState& D, const float* action, const uint8_t* donef, float* obs,
-                                            float* reward, uint8_t* done, float* info, float* lds_par, const NextDyn NX = NextDyn{nullptr, nullptr, nullptr}) {
+                                            float* reward, uint8_t* done, float* info, float* lds_par, const NextDyn NX = NextDyn{nullptr, nullptr, nullptr},
+                                            const TermOut T = TermOut{nullptr, nullptr}) {
   GpuCtx16T<FLAT, KNEE, PLAIN> c;
   if (!make_ctx16_fields(K, D, c, lds_par, K.block0 + xcd_contiguous_block(), threadIdx.x)) return;   // (block0: etg_step_range)
   // the head of a launch is a chain of cold loads (the L2s are invalidated at kernel boundaries): ALL of them -- staged
@@ -1152,9 +1175,13 @@ __device__ __forceinline__ void step16_body(const KCfg& K, const DevState& D, co
   c.prof_last = clock64();
   long long t_begin = c.prof_last;
 #endif
-  control_step16_core(c, K, tp, L, S, D.ring, D.etgp, act, dflag, obs, r, d, info, hybrid ? hyb : nullptr);
+  control_step16_core(c, K, tp, L, S, D.ring, D.etgp, act, dflag, obs, r, d, info, hybrid ? hyb : nullptr, true, nullptr, nullptr,
+                      false, nullptr, AUTO ? T.obs : (float*)nullptr);
   store_ctl16(c, K, S, D.ctl, D.ictl, D.legctl);
-  if (AUTO && d > 0.5f) restart16(c, K, D, NX, L, obs);   // whole 16-lane rows take this branch together (d is the robot's)
+  if (AUTO && d > 0.5f) {   // whole 16-lane rows take this branch together (d is the robot's)
+    if (T.ctx) term_ctx_store(K, D, c.env, c.r, 16, S.step_count, T.ctx);
+    restart16(c, K, D, NX, L, obs);
+  }
   store_state16(c, D.base, D.leg, L);
 #ifdef ETG_PROFILE_PHASES
   if ((c.env & 3) == 0 && c.r == 0 && info) {   // every wave reports, in the info row of its first robot
@@ -1176,9 +1203,9 @@ __global__ void __launch_bounds__(BLOCK) k_step16(KCfg K, DevState D, const floa
 }
 template <bool FLAT, bool KNEE, bool PLAIN>
 __global__ void __launch_bounds__(BLOCK) k_step16_ar(KCfg K, DevState D, const float* action, const uint8_t* donef, float* obs,
-                                                      float* reward, uint8_t* done, float* info, NextDyn NX) {
+                                                      float* reward, uint8_t* done, float* info, NextDyn NX, TermOut T) {
   __shared__ float lds_par[LDS16_FIELDS * BLOCK];
-  step16_body<FLAT, KNEE, PLAIN, true>(K, D, action, donef, obs, reward, done, info, lds_par, NX);
+  step16_body<FLAT, KNEE, PLAIN, true>(K, D, action, donef, obs, reward, done, info, lds_par, NX, T);
 }
 
 // n_steps open-loop control steps of every robot in one launch (rollout_steps16): state, control variables and
@@ -1876,15 +1903,28 @@ __global__ void __launch_bounds__(BLOCK) k_leg_kin(KCfg K, ModelF M, const float
   }
 }
 
-// optional sensors (include/etgsim.h ETG_EXTRA_*): one thread per (robot, column)
-__global__ void k_extra_sensors(KCfg K, ModelF M, DevState D, const float* obs, float* out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int env = i / ETG_EXTRA_DIM, col = i % ETG_EXTRA_DIM;
-  const int N = K.n_env;
-  if (env >= N) return;
+// optional sensors (include/etgsim.h ETG_EXTRA_*): column `col` of a robot's row, from its observation row `orow` [49] and the
+// state the column reads through `src` -- step(): the episode step index of the row (IC_STEP), dyn(k): its dynamic_param row,
+// force(k): the trunk force (set + random push).  The live state (ExtraLive: etg_extra_sensors) or what a restart overwrote
+// (ExtraCtx: a terminal_ctx row, etg_extra_sensors_terminal).
+struct ExtraLive {
+  const DevState& D;
+  int env, N;
+  __device__ int step() const { return D.ictl[(size_t)IC_STEP * N + env]; }
+  __device__ float dyn(int k) const { return D.dyn[(size_t)env * ETG_DYN_DIM + k]; }
+  __device__ float force(int k) const { return D.ctl[(size_t)(CT_FEXT + k) * N + env] + D.ctl[(size_t)(CT_PUSH + k) * N + env]; }
+};
+struct ExtraCtx {
+  const float* row;   // [ETG_TERM_CTX_DIM]
+  __device__ int step() const { return (int)row[ETG_TERM_STEP]; }
+  __device__ float dyn(int k) const { return row[ETG_TERM_DYN + k]; }
+  __device__ float force(int k) const { return row[ETG_TERM_FORCE + k]; }
+};
+template <class Src>
+__device__ __forceinline__ float extra_sensor(const KCfg& K, const ModelF& M, int col, const float* orow, const Src& src) {
   float v = 0.0f;
   if (col < ETG_EXTRA_FOOTPOSE) {            // RBF activations at the ETG time of the row's observation
-    const int k = D.ictl[(size_t)IC_STEP * N + env];
+    const int k = src.step();
     const float t = (float)k * K.etg_dt;
     const float x0 = K.etg_amp * sinf(K.etg_phase0 + t * K.etg_omega), x1 = K.etg_amp * sinf(K.etg_phase1 + t * K.etg_omega);
     const float d0 = x0 - K.etg_u[col][0], d1 = x1 - K.etg_u[col][1];
@@ -1893,7 +1933,7 @@ __global__ void k_extra_sensors(KCfg K, ModelF M, DevState D, const float* obs, 
     const int j = col - ETG_EXTRA_FOOTPOSE, leg = j / 3, k = j % 3;
     float a[3];
     for (int m = 0; m < 3; m++) {
-      const float o = obs[(size_t)env * ETG_OBS_DIM + 13 + 3 * leg + m];
+      const float o = orow[13 + 3 * leg + m];
       a[m] = K.obs_normal ? o * 0.1f + M.pose[3 * leg + m] : o;
     }
     const float l_hip = M.thigh_y[leg], lu = K.upper_len, ll = K.lower_len;
@@ -1904,7 +1944,7 @@ __global__ void k_extra_sensors(KCfg K, ModelF M, DevState D, const float* obs, 
     v = p[k] + M.hip_origin[leg][k];
   } else if (col < ETG_EXTRA_FORCE) {        // inverse of param2dynamic_dict's affine maps (train.py:112-126)
     const int k = col - ETG_EXTRA_DYNAMIC;
-    const float d = D.dyn[(size_t)env * ETG_DYN_DIM + k];
+    const float d = src.dyn(k);
     if (k == 0) v = (d - 40.0f) * 0.1f;
     else if (k == 1) v = (d - 0.2f) * 0.1f;
     else if (k == 2) v = d - 1.5f;
@@ -1913,10 +1953,46 @@ __global__ void k_extra_sensors(KCfg K, ModelF M, DevState D, const float* obs, 
     else if (k < 45) { const float kd0 = ((k - 33) % 3 == 0) ? 1.0f : 2.0f; v = (d - kd0) / kd0; }
     else { const float g0[3] = {0.0f, 0.0f, -10.0f}, gs[3] = {2.0f, 2.0f, 10.0f}; v = (d - g0[k - 45]) / gs[k - 45]; }
   } else if (col < ETG_EXTRA_FORCE + 3) {
-    const int k = col - ETG_EXTRA_FORCE;
-    v = D.ctl[(size_t)(CT_FEXT + k) * N + env] + D.ctl[(size_t)(CT_PUSH + k) * N + env];
+    v = src.force(col - ETG_EXTRA_FORCE);
   }
-  out[(size_t)env * ETG_EXTRA_DIM + col] = v;
+  return v;
+}
+
+// one thread per (robot, column)
+__global__ void k_extra_sensors(KCfg K, ModelF M, DevState D, const float* obs, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int env = i / ETG_EXTRA_DIM, col = i % ETG_EXTRA_DIM;
+  const int N = K.n_env;
+  if (env >= N) return;
+  out[(size_t)env * ETG_EXTRA_DIM + col] = extra_sensor(K, M, col, obs + (size_t)env * ETG_OBS_DIM, ExtraLive{D, env, N});
+}
+
+// the columns of the terminal rows (etg_extra_sensors_terminal): a robot that went on reads the live state, a restarted one
+// (done) its terminal_ctx row
+__global__ void k_extra_sensors_terminal(KCfg K, ModelF M, DevState D, const float* obs, const float* ctx, const uint8_t* done, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int env = i / ETG_EXTRA_DIM, col = i % ETG_EXTRA_DIM;
+  const int N = K.n_env;
+  if (env >= N) return;
+  const float* orow = obs + (size_t)env * ETG_OBS_DIM;
+  out[(size_t)env * ETG_EXTRA_DIM + col] = done[env] ? extra_sensor(K, M, col, orow, ExtraCtx{ctx + (size_t)env * ETG_TERM_CTX_DIM})
+                                                     : extra_sensor(K, M, col, orow, ExtraLive{D, env, N});
+}
+
+// the rows of `obs` of the robots that went on in a 4-lane k_step_ar launch with T.obs (step4_body): their terminal rows
+__global__ void __launch_bounds__(256) k_term_rows(KCfg K, const float* tobs, const uint8_t* done, float* obs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= K.n_env * ETG_OBS_DIM || done[i / ETG_OBS_DIM]) return;
+  obs[i] = tobs[i];
+}
+
+// the terminal_ctx rows of the robots a masked etg_reset is about to restart (etg_step_autoreset_terminal without a cached
+// settle for every robot): the live state after the step, before the reset
+__global__ void __launch_bounds__(256) k_term_ctx(KCfg K, DevState D, const uint8_t* done, float* ctx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int env = i >> 4;
+  if (env >= K.n_env || !done[env]) return;
+  term_ctx_store(K, D, env, i & 15, 16, D.ictl[(size_t)IC_STEP * K.n_env + env], ctx);
 }
 #endif
 
@@ -1927,7 +2003,7 @@ __global__ void k_extra_sensors(KCfg K, ModelF M, DevState D, const float* obs, 
 #define ETG_ARGS_SETTLE KCfg, DevState, const uint8_t*
 #define ETG_ARGS_FINISH KCfg, DevState, const uint8_t*, float*
 #define ETG_ARGS_STEP KCfg, DevState, const float*, const uint8_t*, float*, float*, uint8_t*, float*
-#define ETG_ARGS_STEP_AR KCfg, DevState, const float*, const uint8_t*, float*, float*, uint8_t*, float*, NextDyn
+#define ETG_ARGS_STEP_AR KCfg, DevState, const float*, const uint8_t*, float*, float*, uint8_t*, float*, NextDyn, TermOut
 #define ETG_ARGS_ROLLOUT KCfg, DevState, int, float*, StatOut
 #define ETG_ARGS_TAPE KCfg, DevState, int, const float*, float*, TapeOut
 #define ETG_ARGS_POLICY KCfg, DevState, PolicyW, int, float, float*
@@ -2557,29 +2633,54 @@ extern "C" int etg_step_range(EtgHandle* h, int env0, int count, const float* ac
   return ETG_OK;
 }
 
-extern "C" int etg_step_autoreset(EtgHandle* h, const float* action, const uint8_t* donef, float* obs, float* reward,
-                                  uint8_t* done, float* info, void* stream) {
-  CHECK_HANDLE(h);
+// etg_step_autoreset, and with T.obs its terminal rows (etg_step_autoreset_terminal): T changes nothing else the call writes
+static int step_autoreset(EtgHandle* h, const float* action, const uint8_t* donef, float* obs, float* reward, uint8_t* done,
+                          float* info, TermOut T, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   refresh_all_cached(h);
   if (!h->all_cached) {   // some robot needs a simulated settle: step, then the general reset path masked by the done bytes
     int rc = etg_step(h, action, donef, obs, reward, done, info, stream);
     if (rc != ETG_OK) return rc;
+    if (T.obs) {          // the terminal rows are the step's rows (and their noise) as they stand before the reset
+      HIP_TRY(hipMemcpyAsync(T.obs, obs, (size_t)h->N * ETG_OBS_DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
+      if (T.ctx) hipLaunchKernelGGL(k_term_ctx, dim3((16 * h->N + 255) / 256), dim3(256), 0, s, h->K, h->D, done, T.ctx);
+      HIP_TRY(hipGetLastError());
+    }
     if (h->push_on && (rc = etg_clear_pushes(h, done, stream)) != ETG_OK) return rc;
     return etg_reset(h, done, obs, stream);
   }
   // every robot has a cached settle: step and restart in ONE launch (k_step16_ar / k_step_ar)
   if (int rc = step_checks(h, action, obs, reward, done)) return rc;
   advance_obs_stream(h, 2);                     // two rows per robot at most: the step's (position c) and the reset's (c + 1)
-  hipStream_t s = (hipStream_t)stream;
   if (h->lanes == 16) {
-    LAUNCH16(k_step16_ar, dim3((h->N + 3) / 4), s, h->K, h->D, action, donef, obs, reward, done, info, h->NX);
+    LAUNCH16(k_step16_ar, dim3((h->N + 3) / 4), s, h->K, h->D, action, donef, obs, reward, done, info, h->NX, T);
   } else {
-    LAUNCH4(k_step_ar, dim3(grid_for(h)), s, h->K, h->D, action, donef, obs, reward, done, info, h->NX);
+    LAUNCH4(k_step_ar, dim3(grid_for(h)), s, h->K, h->D, action, donef, obs, reward, done, info, h->NX, T);
   }
-  launch_obs_noise(h, 2, done, obs, s, /*invert=*/1, /*back=*/1);   // the step's rows of the robots that go on
+  launch_obs_noise(h, 2, nullptr, T.obs, s, 0, /*back=*/1);         // the terminal rows: every robot's step row (position c)
+  if (T.obs && h->lanes != 16) {   // (4 lanes: the step's rows went to T.obs only; those of the robots that go on move to obs)
+    hipLaunchKernelGGL(k_term_rows, dim3((h->N * ETG_OBS_DIM + 255) / 256), dim3(256), 0, s, h->K, T.obs, done, obs);
+  } else {
+    launch_obs_noise(h, 2, done, obs, s, /*invert=*/1, /*back=*/1);   // the step's rows of the robots that go on
+  }
   launch_obs_noise(h, 2, done, obs, s);                            // the reset rows
   HIP_TRY(hipGetLastError());
   return ETG_OK;
+}
+
+extern "C" int etg_step_autoreset(EtgHandle* h, const float* action, const uint8_t* donef, float* obs, float* reward,
+                                  uint8_t* done, float* info, void* stream) {
+  CHECK_HANDLE(h);
+  return step_autoreset(h, action, donef, obs, reward, done, info, TermOut{nullptr, nullptr}, stream);
+}
+
+// etg_step_autoreset that keeps every robot's step observation before any restart (include/etgsim_terminal.h)
+extern "C" int etg_step_autoreset_terminal(EtgHandle* h, const float* action, const uint8_t* donef, float* obs, float* terminal_obs,
+                                           float* terminal_ctx, float* reward, uint8_t* done, float* info, void* stream) {
+  CHECK_HANDLE(h);
+  if (!terminal_obs) return fail(ETG_ERR_BAD_ARG, "etg_step_autoreset_terminal: terminal_obs must be non-null");
+  if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_step_autoreset_terminal: call etg_reset first");
+  return step_autoreset(h, action, donef, obs, reward, done, info, TermOut{terminal_obs, terminal_ctx}, stream);
 }
 
 #ifdef ETG_TRACE_TICKS
@@ -2860,6 +2961,19 @@ extern "C" int etg_extra_sensors(EtgHandle* h, const float* obs, float* out, voi
   if (!obs || !out) return fail(ETG_ERR_BAD_ARG, "etg_extra_sensors: null argument");
   const int total = h->N * ETG_EXTRA_DIM;
   hipLaunchKernelGGL(k_extra_sensors, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->K, h->M, h->D, obs, out);
+  HIP_TRY(hipGetLastError());
+  return ETG_OK;
+}
+
+// the extra sensor columns of the terminal rows of the last etg_step_autoreset_terminal (include/etgsim_terminal.h)
+extern "C" int etg_extra_sensors_terminal(EtgHandle* h, const float* terminal_obs, const float* terminal_ctx, const uint8_t* done,
+                                          float* out, void* stream) {
+  CHECK_HANDLE(h);
+  if (!terminal_obs || !terminal_ctx || !done || !out) return fail(ETG_ERR_BAD_ARG, "etg_extra_sensors_terminal: null argument");
+  if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_extra_sensors_terminal: call etg_reset first");
+  const int total = h->N * ETG_EXTRA_DIM;
+  hipLaunchKernelGGL(k_extra_sensors_terminal, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->K, h->M, h->D,
+                     terminal_obs, terminal_ctx, done, out);
   HIP_TRY(hipGetLastError());
   return ETG_OK;
 }

@@ -132,6 +132,10 @@ class _InfoView(dict):
         return len(A.INFO_SLICES)
 
 
+# a row of etg_step_autoreset_terminal's terminal_ctx (include/etgsim_terminal.h ETG_TERM_CTX_DIM): step index, force, dynamics row
+TERM_CTX_DIM = 4 + A.DYN_DIM
+
+
 class FusedKernelUnavailable(ValueError):
     """the configuration is outside what a fused rollout kernel covers (callers may fall back to the stepping loop)"""
 
@@ -486,13 +490,21 @@ class BatchedQuadrupedEnv:
                           "(%s); falling back to a masked reset per control step, which is much slower"
                           % self._lib.etg_last_error().decode(), RuntimeWarning)
 
+    def _row_view(self, rows, extra):
+        """sensor_mode's view of observation rows [N,49]: column selection, then the selected extra sensor columns of `extra`"""
+        o = rows if self._col_idx is None else rows.index_select(1, self._col_idx)
+        if self._xcol_idx is not None:   # optional sensors (train.py:268-271), appended after the 49-float row's columns
+            o = torch.cat([o, extra.index_select(1, self._xcol_idx)], dim=1)
+        return o
+
     def _obs_view(self, reset_mask=None, first=False):
         """the observation the caller sees: sensor_mode column selection, then (optionally) the history stack.
         reset_mask: uint8 [N] of the robots that were just reset (None = all, with first=True)."""
-        o = self.obs if self._col_idx is None else self.obs.index_select(1, self._col_idx)
-        if self._xcol_idx is not None:   # optional sensors (train.py:268-271), appended after the 49-float row's columns
+        extra = None
+        if self._xcol_idx is not None:
             _lib.check(self._lib.etg_extra_sensors(self._h, _ptr(self.obs), _ptr(self.extra), self._stream()))
-            o = torch.cat([o, self.extra.index_select(1, self._xcol_idx)], dim=1)
+            extra = self.extra
+        o = self._row_view(self.obs, extra)
         if self._hist_T == 0:
             return o
         H = self._hist_T * self._hist_dt
@@ -693,11 +705,26 @@ class BatchedQuadrupedEnv:
             raise ValueError("donef must be a bool or have shape [N]")
         return df
 
-    def step(self, action, donef=None, want_info=True, groups=1):
+    def _terminal_buffers(self):
+        """the rows [N,49], sensor context [N,TERM_CTX_DIM] and extra columns [N,84] of etg_step_autoreset_terminal"""
+        if getattr(self, "_term_buf", None) is None:
+            N, dev = self.num_envs, self.device
+            self._term_buf = (torch.zeros(N, A.OBS_DIM, device=dev), torch.zeros(N, TERM_CTX_DIM, device=dev),
+                              torch.zeros(N, A.EXTRA_DIM, device=dev) if self._xcols else None)
+        return self._term_buf
+
+    def step(self, action, donef=None, want_info=True, groups=1, terminal_obs=False):
         """One control step of every robot (env.step of the reference, batched).  groups=G > 1: the batch is stepped as G
-        sub-batches on G streams (identical results); see rollout_policy(fused=False, groups=G) for the loop that gains from it."""
+        sub-batches on G streams (identical results); see rollout_policy(fused=False, groups=G) for the loop that gains from it.
+
+        terminal_obs=True: info["terminal_obs"] is every robot's observation of this step before any restart, in the caller's
+        view (the returned obs's columns, extra sensors and history stack / sequence) -- on an auto_reset env the next_obs of a
+        finished robot's terminal transition, which the returned obs replaces with its reset observation (gymnasium's
+        final_obs).  Present with want_info=False too; everything else the call returns or changes is the same as without it.
+        Without auto_reset it is the returned observation."""
         a = None if action is None else self._f32(action, (self.num_envs, self.action_space.shape[0]), "action")   # NULL = zero residual
         df = self._donef_bytes(donef)
+        term = bool(terminal_obs) and self.auto_reset
         if self._rand_force:
             self._random_pushes()
         # auto_reset: robots whose episode just ended start the next one inside the same call (settle cache -> state, control
@@ -705,10 +732,18 @@ class BatchedQuadrupedEnv:
         # step's, info["reset"] (= done) marks them.  The done bytes are read on the device: no host synchronisation.
         # With random_dynamics the reset robots first draw new parameters, which needs the masked calls of reset().
         fused_reset = self.auto_reset and (not self._rand_dyn or self._nx_on)   # (_nx_on: the next episodes' dynamics are prepared)
-        step_fn = self._lib.etg_step_autoreset if fused_reset else self._lib.etg_step
         if int(groups) > 1:
             self._step_grouped(a, df, want_info, groups)
+        elif fused_reset and term:   # the same launches and results as etg_step_autoreset, plus the rows before the restart
+            t_obs, t_ctx, t_extra = self._terminal_buffers()
+            _lib.check(self._lib.etg_step_autoreset_terminal(self._h, _ptr(a), _ptr(df), _ptr(self.obs), _ptr(t_obs), _ptr(t_ctx),
+                                                             _ptr(self.reward), _ptr(self.done),
+                                                             _ptr(self.info_buf) if want_info else None, self._stream()))
+            if t_extra is not None:
+                _lib.check(self._lib.etg_extra_sensors_terminal(self._h, _ptr(t_obs), _ptr(t_ctx), _ptr(self.done), _ptr(t_extra),
+                                                                self._stream()))
         else:
+            step_fn = self._lib.etg_step_autoreset if fused_reset else self._lib.etg_step
             _lib.check(step_fn(self._h, _ptr(a), _ptr(df), _ptr(self.obs), _ptr(self.reward), _ptr(self.done),
                                _ptr(self.info_buf) if want_info else None, self._stream()))
         self._keep_step = (a, df)
@@ -716,20 +751,34 @@ class BatchedQuadrupedEnv:
         if self.auto_reset:
             if not fused_reset:
                 if self._hist_T > 0:
-                    self._obs_view()                                         # the terminal reading enters the history first
+                    tv = self._obs_view()                                    # the terminal reading enters the history first
+                elif term:                                                   # the step's rows, before the masked reset below
+                    if self._xcol_idx is not None:
+                        _lib.check(self._lib.etg_extra_sensors(self._h, _ptr(self.obs), _ptr(self.extra), self._stream()))
+                    tv = self._row_view(self.obs, self.extra).clone()
                 self._reset_mask = self.done.clone()
                 self.reset(env_ids=self._reset_mask, _keep_offsets=True)
             if want_info:
                 info["reset"] = self.done.view(torch.bool)
             if self._hist_T > 0 and fused_reset:
                 self._obs_view()                                             # the terminal reading enters the history ...
+                older = self._last_seq[:, :-1]
                 self._last_view = self._obs_view(reset_mask=self.done, first=True)   # ... and is cleared for the reset robots
+                if term:   # the robot's older readings and its terminal reading (the reading above is the reset one for restarted robots)
+                    seq = torch.cat([older, self._row_view(t_obs, t_extra).unsqueeze(1)], dim=1)
+                    tv = seq.reshape(self.num_envs, -1) if self._hist_mode == "stack" else seq
             elif fused_reset:
                 self._last_view = self._obs_view()
+                if term:
+                    tv = self._row_view(t_obs, t_extra)
+            if term:
+                info["terminal_obs"] = tv
             if self._nx_on:
                 self._refresh_next_dynamics()
         else:
             self._last_view = self._obs_view()
+            if terminal_obs:
+                info["terminal_obs"] = self._last_view
         return (self._last_view, self.reward, self.done.view(torch.bool) if want_info else self.done, info)
 
     def _step_policy_refusal(self, policy, precision):

@@ -301,48 +301,78 @@ def collect_transitions(env, rpm, max_step, policy=None, action_bound=0.3, mode=
     return ret, ln, infos
 
 
-def collect_continuous(env, rpm, n_steps, policy, action_bound=0.3, mode="sample", noise=None, generator=None, donef=None):
+def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="sample", noise=None, generator=None, donef=None,
+                       fused=None):
     """Continuous collection for SAC (run_train_episode, train.py:129-179, batched without episode boundaries): n_steps control
-    steps of every robot of an auto_reset env through env.step_policy (actor + step + restart in one launch), every step's N
-    transitions appended to `rpm`:
+    steps of every robot of an auto_reset env, every step's N transitions appended to `rpm`:
 
-      obs = the row the actor acted on, action = the unscaled action, reward,
-      next_obs = the step's observation before any restart (info["terminal_obs"]),
+      obs = the observation the action was taken on, action = the unscaled action, reward,
+      next_obs = the step's observation before any restart (the terminal observation of a robot whose episode ended),
       terminal = bootstrap_mask(done, the robot's OWN episode step): 1 - done, 1 from episode step 2000 on (train.py:148-149)
 
-    Robots do not wait for each other: a finished robot restarts in the same launch, and the next call continues every robot's
+    Two paths store the same fields.  The fused one takes one env.step_policy launch per step (actor + step + restart).  The
+    other runs policy.sample / policy.predict on the env's current view, then env.step(action * action_bound,
+    terminal_obs=True): it covers every configuration the simulator steps (the 4-lane mapping, sensor noise, random pushes,
+    extra sensors, observation history, HYBRID).  fused=None takes the fused path where step_policy covers the configuration,
+    True insists on it (FusedKernelUnavailable otherwise), False never takes it.
+
+    Robots do not wait for each other: a finished robot restarts in the same step, and the next call continues every robot's
     episode where this one stopped (the running returns and step counts are read from the simulator at the start).  No host
-    synchronisation.  mode: "sample" (agent.sample; noise [n_steps, N, 12] ~ N(0,1) may be given, else drawn from `generator`)
-    or "predict".  donef [n_steps, N] (bool / uint8, optional): forced episode ends per step, e.g. a time limit (train.py:145
-    `donef=(steps > max_step)`).  Returns (ret [N], len [N]): return and length of the LAST episode of each robot that ended
-    during the call (len 0: none of its episodes ended)."""
+    synchronisation.  mode: "sample" (agent.sample; noise [n_steps, N, action_dim] ~ N(0,1) may be given, else drawn from
+    `generator`), "predict", or "uniform" (U(-1,1) actions without a policy: the warm-up of train.py:140-142).  donef [n_steps, N]
+    (bool / uint8, optional): forced episode ends per step, e.g. a time limit (train.py:145 `donef=(steps > max_step)`).
+    Returns (ret [N], len [N]): return and length of the LAST episode of each robot that ended during the call (len 0: none of
+    its episodes ended)."""
     if not env.auto_reset:
         raise ValueError("collect_continuous needs an env made with auto_reset=True")
-    if mode not in ("predict", "sample"):
-        raise ValueError("mode must be 'predict' or 'sample'")
+    if mode not in ("predict", "sample", "uniform"):
+        raise ValueError("mode must be 'predict', 'sample' or 'uniform'")
+    if mode != "uniform" and policy is None:
+        raise ValueError("mode %r needs a policy" % mode)
+    if mode == "uniform" and fused:
+        raise ValueError("mode 'uniform' has no policy to fuse: fused must be None or False")
     n, dev, T = env.num_envs, env.device, int(n_steps)
+    adim = env.action_space.shape[0]
     if noise is not None:
         if mode != "sample":
             raise ValueError("noise is for mode='sample'")
         noise = torch.as_tensor(noise, dtype=torch.float32, device=dev)
-        if tuple(noise.shape) != (T, n, 12):
-            raise ValueError("noise must be [n_steps, num_envs, 12]")
+        if tuple(noise.shape) != (T, n, adim):
+            raise ValueError("noise must be [n_steps, num_envs, %d]" % adim)
     if donef is not None:
         donef = torch.as_tensor(donef, device=dev).to(torch.uint8).contiguous()
         if tuple(donef.shape) != (T, n):
             raise ValueError("donef must be [n_steps, num_envs]")
+    if fused is None:
+        fused = mode != "uniform" and env._step_policy_refusal(policy, 0) is None
+
+    def step(k):
+        """one control step -> (acted obs, unscaled action, reward, done, next_obs)"""
+        df = None if donef is None else donef[k]
+        if fused:
+            _, reward, done, info, action = env.step_policy(policy, action_bound, mode, noise=None if noise is None else noise[k],
+                                                            donef=df, want_info=False, generator=generator)
+            return info["acted_obs"], action, reward, done, info["terminal_obs"]
+        obs = env._last_view.reshape(n, -1).clone()   # (the env's buffer, or a view of it: the step writes over it)
+        if mode == "uniform":
+            action = torch.rand(n, adim, device=dev, generator=generator) * 2 - 1
+        elif mode == "sample":
+            action = policy.sample(obs, 1.0, noise=None if noise is None else noise[k], generator=generator, return_logp=False)
+        else:
+            action = policy.predict(obs, 1.0)
+        _, reward, done, info = env.step(action * action_bound, donef=df, want_info=False, terminal_obs=True)
+        return obs, action, reward, done, info["terminal_obs"].reshape(n, -1)
+
     run_ret, run_len = env.episode_stats()        # the episodes running now: this call continues them
     last_ret = torch.zeros(n, device=dev)
     last_len = torch.zeros(n, dtype=torch.int32, device=dev)
     for k in range(T):
-        _, reward, done, info, action = env.step_policy(policy, action_bound, mode, noise=None if noise is None else noise[k],
-                                                        donef=None if donef is None else donef[k], want_info=False,
-                                                        generator=generator)
+        obs, action, reward, done, next_obs = step(k)
         d = done.view(-1).to(torch.bool)
         run_ret = run_ret + reward
         run_len = run_len + 1                       # the 1-based episode step of this transition, per robot
         terminal = torch.where(run_len >= BOOTSTRAP_ALWAYS_FROM, torch.ones_like(reward), 1.0 - d.to(torch.float32))
-        rpm.append_batch(info["acted_obs"], action, reward, info["terminal_obs"], terminal)
+        rpm.append_batch(obs, action, reward, next_obs, terminal)
         last_ret = torch.where(d, run_ret, last_ret)
         last_len = torch.where(d, run_len, last_len)
         run_ret = torch.where(d, torch.zeros_like(run_ret), run_ret)
