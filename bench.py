@@ -14,7 +14,12 @@ Timing: the clocks are warmed with >= 200 ms of real ste
 timed, each = reset (untimed), W warm-up steps (untimed), EXACTLY K timed steps bracketed by barrier + synchronize on
 both sides with the max over ranks taken; `value` is the MEDIAN repeat, min / max are reported next to it.  Rank 0
 prints ONE JSON line; `roofline` is the dynamics kernel against the HBM roofline (HIP events on the launch stream,
-inside the timed region), `cpu_baseline` the oracle on the host cores.
+inside the timed region).
+
+A plain run does only what that line's headline needs: set up, warm up, the timed repeats, --dump-outputs, the line.
+Everything measured on its own -- the legs next to `value` (stepwise, groups, auto-reset, fixed sweep counts, presets, config
+3 and its bf16 tile, the ES generation), `cpu_baseline` (the oracle on the host cores), the executed sweep counts, the
+measured HBM copy bandwidth, the stand-alone policy roofline and, for N > 1, `multi_gpu` -- runs with --full only.
 """
 import argparse
 import json
@@ -259,11 +264,14 @@ def main():
                     help="foot friction coefficient of every robot (default: param2dynamic_dict(zeros) = 0.2, on which the open-loop gait skates)")
     ap.add_argument("--no-joint-limits", dest="joint_limits", action="store_false",
                     help="switch the joint-limit stops (a1.py:186-195; on by default, as Bullet enforces the URDF's) off")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need: the legs next to `value`, the CPU baseline, "
+                         "the executed sweep counts, the HBM copy bandwidth, the policy roofline and (N > 1) multi_gpu")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the legs reported next to `value` (stepwise, auto-reset, K = 50, config 3, ES generation): "
-                         "profiling runs, keeps the per-kernel averages clean")
-    ap.add_argument("--no-es-generation", action="store_true", help="skip only the ES-generation leg")
+                    help="with --full: skip the legs reported next to `value` (stepwise, auto-reset, K = 50, config 3, ES "
+                         "generation): profiling runs, keeps the per-kernel averages clean")
+    ap.add_argument("--no-es-generation", action="store_true", help="with --full: skip only the ES-generation leg")
     ap.add_argument("--stepwise", action="store_true",
                     help="time env.step() per control step instead of the fused rollout")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -454,14 +462,14 @@ def main():
                     imbalance["effective_clock_ghz"] = imbalance["kernel_cycles_per_step"] / (kern_ms * 1e-3) * 1e-9
         except Exception as e:                                       # noqa: BLE001 - diagnostics must not lose the line
             imbalance = {"error": repr(e)[:200]}
-    # N > 1: every rank's own median step time, and the one exchange of the path (the all_gather of the returns) on its own
+    # N > 1 (--full): every rank's own median step time, and the one exchange of the path (the all_gather of the returns) on its own
     multi = None
-    if dist is not None:
+    if dist is not None and args.full:
         multi = multi_gpu_report(float(np.median(wall_local)), K, N, dist, dev, env.episode_stats()[0], barrier)
 
-    # ---- legs reported NEXT to `value`, never part of it
+    # ---- legs reported NEXT to `value`, never part of it (--full)
     extra = {}
-    if not args.no_extra_legs and not args.stepwise:
+    if args.full and not args.no_extra_legs and not args.stepwise:
         def leg(e, pol, fz, note, reps=3):
             wl, _, sv = timed_repeats(e, pol, fz, reps)
             m = float(np.median(wl))
@@ -651,8 +659,9 @@ def main():
             out = {**{k: out[k] for k in keys[:i]}, **front, "survivors": out["survivors"], **{k: out[k] for k in keys[i:] if k != "survivors"}}
         if multi is not None:
             out["multi_gpu"] = multi
-        out["roofline"]["hbm_copy_measured_GBps"] = device_copy_bandwidth(dev) / 1e9
-        if policy is not None:
+        if args.full:
+            out["roofline"]["hbm_copy_measured_GBps"] = device_copy_bandwidth(dev) / 1e9
+        if policy is not None and args.full:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(50):
@@ -667,21 +676,22 @@ def main():
                                       "kernel_ms": pol_ms, "dtype": "f32" if args.precision == 0 else "bf16"}
         # sweeps the kernels EXECUTED (per wave: the slowest robot of the 4 / 16 sharing it sets the count), from the info column
         # of plain env.step() calls over the same K steps on the headline robots -- untimed
-        try:
-            env.reset(ETG_w=w, ETG_b=b)
-            acc = torch.zeros((), device=dev)
-            first = None
-            for k in range(K):
-                _, _, _, inf = env.step(None)
-                acc += inf["solver_sweeps"].float().mean()
-                if k == 25:
-                    first = float(acc.item()) / 26.0 / 13.0
-            out["config"]["solver"]["executed_sweeps_per_tick_per_wave"] = {
-                "mean_over_the_%d_steps" % K: float(acc.item()) / K / 13.0, "first_26_steps_mean": first,
-                "source": "info['solver_sweeps'] (ETG_INFO_SWEEPS) of env.step()"}
-        except Exception as e:                                       # noqa: BLE001 - diagnostics must not lose the line
-            out["config"]["solver"]["executed_sweeps_per_tick_per_wave"] = {"error": repr(e)[:200]}
-        if not args.no_cpu_baseline and world == 1:          # the CPU baseline is an N = 1 exercise
+        if args.full:
+            try:
+                env.reset(ETG_w=w, ETG_b=b)
+                acc = torch.zeros((), device=dev)
+                first = None
+                for k in range(K):
+                    _, _, _, inf = env.step(None)
+                    acc += inf["solver_sweeps"].float().mean()
+                    if k == 25:
+                        first = float(acc.item()) / 26.0 / 13.0
+                out["config"]["solver"]["executed_sweeps_per_tick_per_wave"] = {
+                    "mean_over_the_%d_steps" % K: float(acc.item()) / K / 13.0, "first_26_steps_mean": first,
+                    "source": "info['solver_sweeps'] (ETG_INFO_SWEEPS) of env.step()"}
+            except Exception as e:                                   # noqa: BLE001 - diagnostics must not lose the line
+                out["config"]["solver"]["executed_sweeps_per_tick_per_wave"] = {"error": repr(e)[:200]}
+        if args.full and not args.no_cpu_baseline and world == 1:    # the CPU baseline is an N = 1 exercise
             logical = os.cpu_count() or 1
             affinity, quota = usable_cpus()
             hf_cpu = terrain_kw.get("heightfield")

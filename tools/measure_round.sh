@@ -9,11 +9,11 @@ TAG=$1; PART=$2
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 O=$R/gpurun_out/${TAG}_measure; mkdir -p $O
 if [ "$PART" = a ]; then
-  python bench.py > $O/${TAG}_bench_default.json 2> $O/bench_default.err
-  python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench_steps20.json 2> $O/bench_steps20.err
-  python bench.py --config 3 --no-cpu-baseline > $O/${TAG}_bench_config3.json 2> $O/bench_config3.err
-  python bench.py --config 3 --steps 20 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_config3_steps20.json 2>> $O/bench_config3.err
-  python bench.py --config 5 --steps 200 --no-cpu-baseline > $O/${TAG}_bench_config5.json 2> $O/bench_config5.err
+  python bench.py --full > $O/${TAG}_bench_default.json 2> $O/bench_default.err
+  python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench_steps20.json 2> $O/bench_steps20.err
+  python bench.py --full --config 3 --no-cpu-baseline > $O/${TAG}_bench_config3.json 2> $O/bench_config3.err
+  python bench.py --full --config 3 --steps 20 --warmup 5 --no-cpu-baseline > $O/${TAG}_bench_config3_steps20.json 2>> $O/bench_config3.err
+  python bench.py --full --config 5 --steps 200 --no-cpu-baseline > $O/${TAG}_bench_config5.json 2> $O/bench_config5.err
   for c in 2 3 5; do
     bash tools/profile_gpu.sh ${TAG}_cfg$c --config $c > $O/profile_cfg$c.log 2>&1
     f=$(find gpurun_out/prof_${TAG}_cfg$c -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/${TAG}_cfg${c}_kernel_stats.csv

@@ -13,7 +13,7 @@ STEPS=50
 mkdir -p $OUT $R/gpurun_out
 run() { # name counters...
   name=$1; shift
-  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -o pmc -- python $R/bench.py --steps $STEPS --warmup 5 --repeats 2 --no-cpu-baseline --no-extra-legs $PMC_BENCH_ARGS > $OUT/$name.log 2>&1 || echo "pass $name failed"
+  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -o pmc -- python $R/bench.py --steps $STEPS --warmup 5 --repeats 2 --full --no-cpu-baseline --no-extra-legs $PMC_BENCH_ARGS > $OUT/$name.log 2>&1 || echo "pass $name failed"
 }
 # PMC_PASSES selects the counter groups (default: all five)
 PASSES=${PMC_PASSES:-"fetch write valu lds mfma"}

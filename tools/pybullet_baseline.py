@@ -3,7 +3,7 @@
 
 The reference's simulator is pybullet driving pybullet_data/a1/a1.urdf through rlschool; neither ships with
 /root/reference and neither is installed in this image, so this script normally prints that pybullet is
-unavailable and bench.py's `cpu_baseline` stays the repo's own oracle (kind "port").  Where pybullet IS
+unavailable and the `cpu_baseline` of bench.py --full stays the repo's own oracle (kind "port").  Where pybullet IS
 installed it times the loop the reference runs per control step -- restated from minitaur.py:242-260 (sub-step
 loop), :904-947 (PD -> TORQUE_CONTROL), :1151-1170 (state read-back) -- with this repo's own harness (no
 reference code is imported), and can dump joint/base trajectories for a parity look at the oracle.

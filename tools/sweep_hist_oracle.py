@@ -1,6 +1,6 @@
 """Sweep-count histograms of the contact solver's stopping rule (EtgConfig.solver_residual, the library default: at most 50
 sweeps, squared row residual <= 1e-7) on the BASELINE workloads, from the ORACLE -- the rule's definition, per robot and tick
-(the kernels execute, per wave, the count of the slowest robot sharing the wave: bench.py reports that next to it).
+(the kernels execute, per wave, the count of the slowest robot sharing the wave: bench.py --full reports that next to it).
 256 robots x 400 control steps each; CPU only.  usage: python tools/sweep_hist_oracle.py > profiles/r03_sweep_histograms.txt"""
 import os
 import sys
