@@ -5,16 +5,30 @@ checkpoint format (`torch.save(state_dict)` with actor_model.* keys, mujoco_agen
 w, b; train.py:386-390).
 
     python examples/evaluate_policy.py --actor model.pt --etg ETG_models/Slope_ETG.npz --task stairstair
-Without --actor a random-initialised actor of the reference architecture is used (BASELINE config 3)."""
+Without --actor a random-initialised actor of the reference architecture is used (BASELINE config 3).  --frames DIR writes
+robot 0's 640 x 480 frame of every step as DIR/img{step}.png (train.py:196-199; binary PPM when PIL is absent)."""
 import argparse
 import os
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from paddlerobotics_amd.env import make_env  # noqa: E402
 from paddlerobotics_amd.policy import MfmaPolicy  # noqa: E402
+
+
+def save_frame(path, rgb):
+    """rgb [h,w,3] uint8 -> path.png (PIL) or path.ppm"""
+    try:
+        from PIL import Image
+    except ImportError:
+        h, w, _ = rgb.shape
+        with open(path + ".ppm", "wb") as f:
+            f.write(b"P6 %d %d 255\n" % (w, h) + np.ascontiguousarray(rgb).tobytes())
+        return
+    Image.fromarray(rgb).save(path + ".png")
 
 
 def main():
@@ -26,7 +40,10 @@ def main():
     ap.add_argument("--max-step", type=int, default=600)          # train.py:373
     ap.add_argument("--act-bound", type=float, default=0.3)       # train.py:488
     ap.add_argument("--student", action="store_true", help="46-float observation (no BaseDisplacement), BCtrain.py:53-59")
+    ap.add_argument("--frames", type=str, default="", help="write robot 0's frame of every step to this directory")
     args = ap.parse_args()
+    if args.frames:
+        os.makedirs(args.frames, exist_ok=True)
     env = make_env("Quadrupedal", num_envs=args.num_envs, device="cuda:0", task=args.task, ETG_path=args.etg,
                    sensor_mode={"dis": 0} if args.student else None)
     obs_dim = env.observation_space.shape[0]
@@ -40,6 +57,8 @@ def main():
     for steps in range(1, args.max_step + 2):
         obs, rew, done, info = env.step(pol.predict(obs, args.act_bound), donef=(steps > args.max_step))
         success += (info["velx"] >= 0.3).float() * (1 - env.done.float())        # train.py:156
+        if args.frames:                                                             # train.py:196-199
+            save_frame(os.path.join(args.frames, "img%d" % steps), env.render([0], 640, 480)[0, :, :, :3].cpu().numpy())
     ret, length = env.episode_stats()
     print("episodes %d | return mean %.1f max %.1f | length mean %.1f | survivors %.1f %% | mean x %.2f m" %
           (args.num_envs, ret.mean().item(), ret.max().item(), length.float().mean().item(),

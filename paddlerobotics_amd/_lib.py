@@ -1,5 +1,5 @@
-"""ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h and include/etgsim_terminal.h
-(paddlerobotics_amd/csrc/libetgsim.so).
+"""ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h, include/etgsim_terminal.h and
+include/etgsim_render.h (paddlerobotics_amd/csrc/libetgsim.so).
 
 There is no CPU fallback: if the library is missing this module raises, and if no HIP
 device is visible etg_create() fails with ETG_ERR_NO_DEVICE.
@@ -25,6 +25,8 @@ SYMBOLS = [
 STEP_POLICY_SYMBOLS = ["etg_step_policy"]
 # ... and include/etgsim_terminal.h
 TERMINAL_SYMBOLS = ["etg_step_autoreset_terminal", "etg_extra_sensors_terminal"]
+# ... and include/etgsim_render.h
+RENDER_SYMBOLS = ["etg_render"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 
@@ -89,6 +91,7 @@ def load():
     lib.etg_step_policy.argtypes = [vp, vp, C.c_float, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_step_autoreset_terminal.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_extra_sensors_terminal.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.etg_render.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.etg_rollout_actions.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_prepare_next_dynamics.argtypes = [vp, vp, vp, vp]
     lib.etg_next_dynamics_pending.argtypes = [vp, vp, vp]

@@ -2108,6 +2108,9 @@ ETG_INSTP4(k_rollout_policy4, true, 3, 4, 5, 6, 7, 1, ETG_ARGS_POLICY)
 }  // namespace etg
 
 #if ETG_TU_HOST
+#include "render_core.h"
+#include "../../include/etgsim_render.h"
+
 // ====================================================================== C ABI
 using namespace etg;
 
@@ -2142,6 +2145,9 @@ struct EtgHandle {
   unsigned inval_seq;
   volatile unsigned* cached_report;   // pinned host memory, also mapped on the device (cached_report_dev)
   unsigned* cached_report_dev;
+  // etg_render: lowest / highest height of the heightfield, taken at the first render after etg_set_heightfield
+  bool hf_range_ok;
+  float hf_lo, hf_hi;
 };
 
 static thread_local std::string g_err;
@@ -2221,7 +2227,9 @@ extern "C" int etg_create(const EtgConfig* cfg, const EtgRobotModel* model, int 
   h->nx_mask = nullptr;
   h->wave_cycles = nullptr;
   h->wc_cap = h->wc_launches = h->wc_waves = 0;
-  h->rollout_chunk = 400;   // (a 400-step launch lasts ~37 ms; fewer launches = fewer chip-wide barriers: 93.3 us per step against 94.0 at 50)
+  h->hf_range_ok = false;
+  h->hf_lo = h->hf_hi = 0.0f;
+  h->rollout_chunk = 400;  // (a 400-step launch lasts ~37 ms; fewer launches = fewer chip-wide barriers: 93.3 us per step against 94.0 at 50)
   if (const char* e = getenv("ETG_ROLLOUT_CHUNK")) {
     const int v = atoi(e);
     if (v >= 1 && v <= 100000) h->rollout_chunk = v;
@@ -2368,6 +2376,7 @@ extern "C" int etg_set_heightfield(EtgHandle* h, const float* heights, void* str
   h->all_cached = false;
   h->inval_seq++;
   h->K.hf = h->hf;
+  h->hf_range_ok = false;
   return ETG_OK;
 }
 
@@ -2953,6 +2962,34 @@ extern "C" int etg_leg_kinematics(EtgHandle* h, const float* q, int n, float* fo
   if (!q || !foot || n <= 0) return fail(ETG_ERR_BAD_ARG, "etg_leg_kinematics: bad arguments");
   hipLaunchKernelGGL(k_leg_kin, dim3((n + 3) / 4), dim3(BLOCK), 0, (hipStream_t)stream, h->K, h->M, q, n, foot, jac);
   HIP_TRY(hipGetLastError());
+  return ETG_OK;
+}
+
+// camera images (include/etgsim_render.h): the handle's terrain and geometry packed for the kernel of etg_render.hip
+extern "C" int etg_render(EtgHandle* h, const float* state, const int* env_ids, int n, const float* view, const float* proj, int width,
+                          int height, uint8_t* rgba, float* depth, int* seg, void* stream) {
+  CHECK_HANDLE(h);
+  if (!state || !env_ids || !view || !proj || !rgba) return fail(ETG_ERR_BAD_ARG, "etg_render: null argument");
+  if (n <= 0) return fail(ETG_ERR_BAD_ARG, "etg_render: n must be positive");
+  if (width < 1 || width > 4096 || height < 1 || height > 4096) return fail(ETG_ERR_BAD_ARG, "etg_render: width and height must be in 1..4096");
+  if ((uintptr_t)rgba % 4) return fail(ETG_ERR_BAD_ARG, "etg_render: rgba must be 4-byte aligned");
+  const long long tiles = (long long)((width + 15) / 16) * ((height + 15) / 16);
+  if (tiles * n > (1ll << 24) - 1) return fail(ETG_ERR_BAD_ARG, "etg_render: too many pixels for one call");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> ids(n);
+  HIP_TRY(hipMemcpyAsync(ids.data(), env_ids, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int i = 0; i < n; i++)
+    if (ids[i] < 0 || ids[i] >= h->N) return fail(ETG_ERR_BAD_ARG, "etg_render: env id outside [0, N)");
+  if (h->K.terrain == 1 && h->hf && !h->hf_range_ok) {
+    std::vector<float> hh((size_t)h->K.hf_nx * h->K.hf_ny * h->K.hf_bands);
+    HIP_TRY(hipMemcpyAsync(hh.data(), h->hf, hh.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    render::height_range(hh.data(), hh.size(), h->hf_lo, h->hf_hi);
+    h->hf_range_ok = true;
+  }
+  const render::RenderScene S = render::make_render_scene(h->K, h->M, h->hf, h->hf_lo, h->hf_hi);
+  HIP_TRY(etg_render_launch(S, state, env_ids, n, view, proj, width, height, rgba, depth, seg, s));
   return ETG_OK;
 }
 

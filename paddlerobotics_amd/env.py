@@ -185,8 +185,8 @@ class BatchedQuadrupedEnv:
                  observation_noise_stdev=None, body_contacts=2, body_friction=0.5, knee_radius=0.02, joint_limits=True,
                  auto_reset=False, random_dynamics_refresh=256, warmstart=0.1, warmstart_friction=0.0, contact_slop=1e-5,
                  foot_restitution=0.0, motor_torque_limits=None, solver_preset=None, body_blend=1e-3, **unused):
-        if render:
-            raise ValueError("render is not supported by the batched GPU simulator")
+        # render=True (train.py:278,305: evaluation) only opens pybullet's GUI in the reference; frames are taken explicitly
+        # there (p.getCameraImage) and here (render(), SingleRobotEnv.getCameraImage), so it changes nothing about stepping
         if int(ETG_H) != A.RBF_H:
             raise ValueError("ETG_H must be %d" % A.RBF_H)
         if task not in TASKS:
@@ -1072,6 +1072,43 @@ class BatchedQuadrupedEnv:
         _lib.check(self._lib.etg_set_contact_impulses(self._h, _ptr(lam), self._stream()))
         self._keep_lam = lam
 
+    # ---- camera images (include/etgsim_render.h) --------------------------------
+    def render(self, env_ids=None, width=320, height=240, view_matrix=None, projection_matrix=None, depth=False,
+               segmentation=False, states=None):
+        """Camera images of robots, each on its own terrain band, as device tensors: rgba [n,H,W,4] uint8, and with
+        depth=True / segmentation=True also depth [n,H,W] float32 (OpenGL depth-buffer values, 1 = sky) and seg [n,H,W] int32
+        (-1 sky, 0 terrain, 1 trunk, 2 + 4 leg + {0 hip, 1 thigh, 2 calf, 3 foot}) -- returned as (rgba, depth, seg) with the
+        ones not asked for left out.  env_ids: robot indices or a boolean [N] mask (None: all); states [n,37]: rows to draw
+        instead of the live state (e.g. a stored trajectory); view_matrix / projection_matrix: [16] or [n,16] column-major as
+        pybullet's (render.compute_view_matrix ...), default the follow camera of render.follow_view_matrix."""
+        from . import render as R
+        dev = self.device
+        if env_ids is None:
+            ids = torch.arange(self.num_envs, device=dev)
+        else:
+            ids = torch.as_tensor(env_ids, device=dev)
+            ids = ids.nonzero().reshape(-1) if ids.dtype == torch.bool else ids.reshape(-1)
+        ids = ids.to(torch.int32).contiguous()
+        n = ids.numel()
+        st = self.get_state()[ids.long()] if states is None else self._f32(states, (n, A.STATE_DIM), "states")
+        W, H = int(width), int(height)
+
+        def mats(m, default, what):
+            m = default() if m is None else m
+            t = torch.as_tensor(m, dtype=torch.float32, device=dev).reshape(-1, 16)
+            if t.shape[0] not in (1, n):
+                raise ValueError("%s must be [16] or [n,16]" % what)
+            return t.expand(n, 16).contiguous()
+        view = mats(view_matrix, lambda: R.follow_view_matrix(st[:, :3]), "view_matrix")
+        proj = mats(projection_matrix, lambda: R.default_projection_matrix(W, H), "projection_matrix")
+        rgba = torch.empty(n, H, W, 4, dtype=torch.uint8, device=dev)
+        dep = torch.empty(n, H, W, device=dev) if depth else None
+        seg = torch.empty(n, H, W, dtype=torch.int32, device=dev) if segmentation else None
+        _lib.check(self._lib.etg_render(self._h, _ptr(st), _ptr(ids), n, _ptr(view), _ptr(proj), W, H, _ptr(rgba), _ptr(dep),
+                                        _ptr(seg), self._stream()))
+        out = (rgba,) + ((dep,) if depth else ()) + ((seg,) if segmentation else ())
+        return out[0] if len(out) == 1 else out
+
 
 class SingleRobotEnv:
     """The reference's own scalar surface over a batch of ONE robot, for the scripts that drive a single env object and
@@ -1113,6 +1150,19 @@ class SingleRobotEnv:
         a = torch.as_tensor(np.asarray(action, dtype=np.float32).reshape(1, -1), device=b.device)
         obs, reward, done, info = b.step(a, donef=bool(donef))
         return obs[0].detach().cpu().numpy(), float(reward[0].item()), bool(done[0].item()), self._info(info)
+
+    def getCameraImage(self, width, height, viewMatrix=None, projectionMatrix=None, **unused):
+        """pybullet.getCameraImage's tuple (width, height, rgba [h,w,4] uint8, depth [h,w] float32, seg [h,w] int32) as numpy
+        arrays (train.py:197); the default camera is the follow camera.  Light, renderer and flag keywords are accepted and
+        ignored."""
+        rgba, depth, seg = self.batched.render([0], width, height, viewMatrix, projectionMatrix, depth=True, segmentation=True)
+        return int(width), int(height), rgba[0].cpu().numpy(), depth[0].cpu().numpy(), seg[0].cpu().numpy()
+
+    def render(self, mode="rgb_array", width=320, height=240):
+        """gym-style frame: [h,w,3] uint8"""
+        if mode != "rgb_array":
+            raise NotImplementedError("only mode='rgb_array' exists here")
+        return self.batched.render([0], width, height)[0, :, :, :3].cpu().numpy()
 
     def close(self):
         self.batched.close()
