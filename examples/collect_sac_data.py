@@ -4,7 +4,8 @@ QuadrupedalRobots/ETGRL/train.py (run_train_episode :129-179 and run_EStrain_epi
 episodes with uniform actions, then episodes with the stochastic actor; every transition of a robot whose episode is
 still running goes to a DeviceReplayMemory in HBM, and `sample_batch` hands the learner device tensors.
 
-The learner itself (alg/sac.py) is out of scope here; the loop below shows where `agent.learn(*batch)` plugs in.
+The learner itself (alg/sac.py) is paddlerobotics_amd/sac.py (DeviceSAC), and examples/train_sac.py is the whole loop; the loop
+below shows where `agent.learn(*batch)` plugs in.
 Usage: python examples/collect_sac_data.py [--num-envs 1024] [--episodes 3] [--max-step 100]"""
 import argparse
 import os

@@ -1,0 +1,61 @@
+#!/usr/bin/env python
+"""The reference's SAC training loop (QuadrupedalRobots/ETGRL/train.py: run_train_episode :129-179, the learn call :163-167,
+evaluation :182-211) on one GPU with nothing waiting for the host: warm-up with uniform actions, then k control steps of every
+robot with the stochastic actor (collect_continuous on an auto_reset env) alternating with learn_from on the replay memory, the
+actor the simulator uses being the one the learner has just updated (learner.policy).
+
+Usage: python examples/train_sac.py [--num-envs 4096] [--iters 200] [--collect-steps 1] [--utd 4] [--eval-every 50] [--out sac.pt]
+--utd: updates per control step (the reference does one update of 256 rows per transition of its single robot)."""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from paddlerobotics_amd.env import make_env  # noqa: E402
+from paddlerobotics_amd.replay import DeviceReplayMemory, collect_continuous  # noqa: E402
+from paddlerobotics_amd.sac import DeviceSAC  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--num-envs", type=int, default=4096)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--collect-steps", type=int, default=1)
+    ap.add_argument("--utd", type=int, default=4)
+    ap.add_argument("--warmup-steps", type=int, default=4)       # control steps of uniform actions (WARMUP_STEPS, train.py:33)
+    ap.add_argument("--batch-size", type=int, default=256)       # BATCH_SIZE, train.py:37
+    ap.add_argument("--memory-size", type=int, default=int(1e6))   # MEMORY_SIZE, train.py:35
+    ap.add_argument("--eval-every", type=int, default=50)
+    ap.add_argument("--eval-steps", type=int, default=200)
+    ap.add_argument("--out", type=str, default="sac.pt")
+    ap.add_argument("--device", type=str, default="cuda:0")
+    args = ap.parse_args()
+    env = make_env("Quadrupedal", num_envs=args.num_envs, device=args.device, auto_reset=True)
+    evl = make_env("Quadrupedal", num_envs=min(args.num_envs, 256), device=args.device)
+    obs_dim, act_dim = env.observation_space.shape[0], env.action_space.shape[0]
+    learner = DeviceSAC(obs_dim, act_dim, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, device=args.device)
+    rpm = DeviceReplayMemory(args.memory_size, obs_dim, act_dim, device=args.device)
+    env.reset()
+    collect_continuous(env, rpm, args.warmup_steps, policy=learner.policy, action_bound=0.3, mode="uniform")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(1, args.iters + 1):
+        collect_continuous(env, rpm, args.collect_steps, policy=learner.policy, action_bound=0.3, mode="sample")
+        losses = learner.learn_from(rpm, args.batch_size, n_updates=args.utd * args.collect_steps)
+        if it % args.eval_every == 0 or it == args.iters:
+            evl.reset()
+            ret, length = evl.rollout_policy(learner.policy, args.eval_steps, act_scale=0.3)
+            dt = time.perf_counter() - t0               # the .item() calls below are this loop's only host synchronisations
+            print("iter %d: %.0f control steps/s, %.0f updates/s, memory %d, critic loss %.4f, actor loss %.4f, eval return %.3f"
+                  % (it, it * args.collect_steps / dt, it * args.collect_steps * args.utd / dt, rpm.size(),
+                     losses[-1, 0].item(), losses[-1, 1].item(), ret.mean().item()))
+            learner.save(args.out)                      # the reference's checkpoint format: loads into its MujocoModel
+    env.close()
+    evl.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -1,5 +1,5 @@
-"""ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h, include/etgsim_terminal.h and
-include/etgsim_render.h (paddlerobotics_amd/csrc/libetgsim.so).
+"""ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h, include/etgsim_terminal.h,
+include/etgsim_render.h and include/etgsim_sac.h (paddlerobotics_amd/csrc/libetgsim.so).
 
 There is no CPU fallback: if the library is missing this module raises, and if no HIP
 device is visible etg_create() fails with ETG_ERR_NO_DEVICE.
@@ -27,6 +27,9 @@ STEP_POLICY_SYMBOLS = ["etg_step_policy"]
 TERMINAL_SYMBOLS = ["etg_step_autoreset_terminal", "etg_extra_sensors_terminal"]
 # ... and include/etgsim_render.h
 RENDER_SYMBOLS = ["etg_render"]
+# ... and include/etgsim_sac.h
+SAC_SYMBOLS = ["etg_sac_create", "etg_sac_destroy", "etg_sac_set_hyper", "etg_sac_load", "etg_sac_store", "etg_sac_load_opt",
+               "etg_sac_store_opt", "etg_sac_learn", "etg_sac_learn_replay", "etg_sac_grads", "etg_sac_sync_policy"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 
@@ -92,6 +95,17 @@ def load():
     lib.etg_step_autoreset_terminal.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_extra_sensors_terminal.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.etg_render.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.etg_sac_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
+    lib.etg_sac_destroy.argtypes = [vp]
+    lib.etg_sac_set_hyper.argtypes = [vp] + [C.c_double] * 5
+    lib.etg_sac_load.argtypes = [vp, C.POINTER(vp), i32, vp]
+    lib.etg_sac_store.argtypes = [vp, C.POINTER(vp), i32, vp]
+    lib.etg_sac_load_opt.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.etg_sac_store_opt.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.etg_sac_learn.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.etg_sac_learn_replay.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.etg_sac_grads.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(vp), vp]
+    lib.etg_sac_sync_policy.argtypes = [vp, vp, vp]
     lib.etg_rollout_actions.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_prepare_next_dynamics.argtypes = [vp, vp, vp, vp]
     lib.etg_next_dynamics_pending.argtypes = [vp, vp, vp]

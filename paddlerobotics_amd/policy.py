@@ -61,6 +61,11 @@ class MfmaPolicy:
                 self._std = st
                 break
 
+    def _mark_loaded(self, std=True):
+        """the packed weight images were written on the device by someone else (etg_sac_sync_policy): predict() / sample() may run"""
+        self._w = ("device",)
+        self._std = ("device",) if std else None
+
     def restore(self, path):
         self.load_state_dict(torch.load(path, map_location="cpu"))
 
