@@ -10,8 +10,9 @@
 // possible (v_add_f32_dpp by the compiler, v_fmac_f32_dpp by inline asm); the 4-lane contact operator's 4x4
 // blocks are v_mfma_f32_4x4x1.  LDS holds each lane's private per-step parameter column (no barriers anywhere);
 // the per-tick constants go straight from HBM to registers.  A reset restores the cached 500-tick settle.
-// Every step / rollout / reset kernel has compile-time variants picked per launch (LAUNCH16 / LAUNCH4): flat ground
-// vs heightfield, body contacts, and PLAIN (the default robot layer with its unused options compiled out).
+// Every step / rollout / reset kernel has compile-time variants: flat ground vs heightfield, body contacts, and PLAIN (the
+// default robot layer with its unused options compiled out).  etg_layout.h lists them and picks one per launch (dispatch16 /
+// dispatch4, which LAUNCH16 / LAUNCH4 and the test emulation call).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -1998,7 +1999,7 @@ __global__ void __launch_bounds__(256) k_term_ctx(KCfg K, DevState D, const uint
 
 // ---- the tick kernels' instantiations, one row per kernel family, one SLOT per instantiation.  A slot belongs to part
 // 1 + (slot - 1) % (ETG_TU_PARTS - 1): that part instantiates the kernel, every other part (the host side included) only
-// declares it.  The combinations are the ones DISPATCH16 / LAUNCH4 / LAUNCH_POLICY* launch; a launch of a combination that
+// declares it.  The combinations are the ones dispatch16 / dispatch4 (etg_layout.h) can pick; a launch of a combination that
 // is missing here fails at link time (undefined __device_stub__), not at run time.
 #define ETG_ARGS_SETTLE KCfg, DevState, const uint8_t*
 #define ETG_ARGS_FINISH KCfg, DevState, const uint8_t*, float*
@@ -2047,7 +2048,7 @@ __global__ void __launch_bounds__(256) k_term_ctx(KCfg K, DevState D, const uint
 #else
 #define ETG_TPL_7 extern template
 #endif
-// 16-lane families: <FLAT, KNEE, PLAIN> in the order of DISPATCH16
+// 16-lane families: <FLAT, KNEE, PLAIN> in the order of ETG_VARIANTS16 (etg_layout.h)
 #define ETG_INST16(KERN, S0, S1, S2, S3, S4, S5, ...)                          \
   ETG_TPL_##S0 __global__ void KERN<true, true, true>(__VA_ARGS__);            \
   ETG_TPL_##S1 __global__ void KERN<true, false, true>(__VA_ARGS__);           \
@@ -2063,7 +2064,7 @@ __global__ void __launch_bounds__(256) k_term_ctx(KCfg K, DevState D, const uint
   ETG_TPL_##S3 __global__ void KERN<false, BF, true, true>(__VA_ARGS__);       \
   ETG_TPL_##S4 __global__ void KERN<false, BF, false, true>(__VA_ARGS__);      \
   ETG_TPL_##S5 __global__ void KERN<false, BF, true, false>(__VA_ARGS__);
-// 4-lane families: <FLAT, PLAIN, BODY> in the order of LAUNCH4
+// 4-lane families: <FLAT, PLAIN, BODY> in the order of ETG_VARIANTS4 (etg_layout.h)
 #define ETG_INST4(KERN, S0, S1, S2, S3, S4, S5, S6, S7, ...)                   \
   ETG_TPL_##S0 __global__ void KERN<true, false, 3>(__VA_ARGS__);              \
   ETG_TPL_##S1 __global__ void KERN<false, false, 3>(__VA_ARGS__);             \
@@ -2073,7 +2074,7 @@ __global__ void __launch_bounds__(256) k_term_ctx(KCfg K, DevState D, const uint
   ETG_TPL_##S5 __global__ void KERN<true, false, 0>(__VA_ARGS__);              \
   ETG_TPL_##S6 __global__ void KERN<false, true, 0>(__VA_ARGS__);              \
   ETG_TPL_##S7 __global__ void KERN<false, false, 0>(__VA_ARGS__);
-// closed-loop 4-lane family: <FLAT, BF16, PLAIN, BODY> in the order of LAUNCH_POLICY4
+// closed-loop 4-lane family: <FLAT, BF16, PLAIN, BODY> in the order of ETG_VARIANTS4 without BODY == 3 (etg_rollout_policy refuses it)
 #define ETG_INSTP4(KERN, BF, S0, S1, S2, S3, S4, S5, ...)                      \
   ETG_TPL_##S0 __global__ void KERN<true, BF, false, 1>(__VA_ARGS__);          \
   ETG_TPL_##S1 __global__ void KERN<false, BF, false, 1>(__VA_ARGS__);         \
@@ -2307,44 +2308,24 @@ static inline void launch_rollout_noise(EtgHandle* h, int n, float* obs, hipStre
   hipLaunchKernelGGL(k_add_noise_rows, dim3((16 * h->N + 255) / 256), dim3(256), 0, s, h->K, h->D, h->K.noise_call, (unsigned)n, obs);
 }
 
-// the instantiations of a 16-lane kernel: {flat ground, heightfield} x {plain robot layer + body rows (the default), plain
-// robot layer with toe spheres only, all options + body rows}.  The last one also serves body_contacts = 0 of the all-options
-// layer (the rows are switched off at run time: KCfg.knee == 0), so a kernel still has six instantiations.
-#define DISPATCH16(X)                                                                                                 \
-  do {                                                                                                                \
-    const bool pl_ = plain_config(h->K), kn_ = h->K.knee != 0, fl_ = h->K.terrain == 0;                               \
-    if (fl_ && pl_ && kn_) X(true, true, true);                                                                       \
-    else if (fl_ && pl_) X(true, false, true);                                                                        \
-    else if (fl_) X(true, true, false);                                                                               \
-    else if (pl_ && kn_) X(false, true, true);                                                                        \
-    else if (pl_) X(false, false, true);                                                                              \
-    else X(false, true, false);                                                                                       \
-  } while (0)
+// A tick kernel is launched in the variant that dispatch16 / dispatch4 (etg_layout.h: the lists of the variants and the rules of
+// the choice) pick for the handle's configuration.  These are macros only because a kernel template's name cannot be passed as a
+// value; every combination a launch can name is in the instantiation table above, or the library does not link.
+#define ETG_V(c) decltype(c)::value
 #define LAUNCH16(KERN, grid, stream, ...)                                                                             \
-  do {                                                                                                                \
-    auto launch_ = [&](auto f_, auto k_, auto p_) {                                                                   \
-      hipLaunchKernelGGL((KERN<decltype(f_)::value, decltype(k_)::value, decltype(p_)::value>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__); \
-    };                                                                                                                \
-    DISPATCH16(LAUNCH16_X_);                                                                                          \
-  } while (0)
-#define LAUNCH16_X_(F_, K_, P_) launch_(std::integral_constant<bool, F_>{}, std::integral_constant<bool, K_>{}, std::integral_constant<bool, P_>{})
-
-// 4-lane kernels: {flat ground, heightfield} x {plain robot layer, all options, all options + 1 body row per leg, + 3 body rows}.
-// A plain robot layer WITH body rows (the default configuration beyond 8192 robots) runs the all-options instantiation: the
-// PLAIN specialisation is worth ~3 % where the tick fits the register file, but the 4-lane tick with body rows is at the
-// 512-register budget with 528-544 B of scratch either way (profiles/r06_isa_baseline.json: k_rollout<flat, all options, 1>), its
-// time is the spills' and the sweeps', and every further instantiation of it costs ~70 s of build for the six 4-lane kernels.
+  dispatch16(h->K, [&](auto f_, auto k_, auto p_) {                                                                   \
+    hipLaunchKernelGGL((KERN<ETG_V(f_), ETG_V(k_), ETG_V(p_)>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__);           \
+  })
 #define LAUNCH4(KERN, grid, stream, ...)                                                                              \
+  dispatch4(h->K, [&](auto f_, auto p_, auto b_) {                                                                    \
+    hipLaunchKernelGGL((KERN<ETG_V(f_), ETG_V(p_), ETG_V(b_)>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__);           \
+  })
+// the 16-lane kernel or its 4-lane counterpart; tick_grid(h): the mapping's grid for the whole batch
+static dim3 tick_grid(const EtgHandle* h) { return dim3(h->lanes == 16 ? (h->N + 3) / 4 : grid_for(h)); }
+#define LAUNCH_TICK(KERN16, KERN4, grid, stream, ...)                                                                 \
   do {                                                                                                                \
-    const bool pl_ = plain_config(h->K);                                                                              \
-    if (h->K.knee == 3 && h->K.terrain == 0) hipLaunchKernelGGL((KERN<true, false, 3>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__); \
-    else if (h->K.knee == 3) hipLaunchKernelGGL((KERN<false, false, 3>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__);  \
-    else if (h->K.knee && h->K.terrain == 0) hipLaunchKernelGGL((KERN<true, false, 1>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__); \
-    else if (h->K.knee) hipLaunchKernelGGL((KERN<false, false, 1>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__);       \
-    else if (h->K.terrain == 0 && pl_) hipLaunchKernelGGL((KERN<true, true>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__);  \
-    else if (h->K.terrain == 0) hipLaunchKernelGGL((KERN<true, false>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__);   \
-    else if (pl_) hipLaunchKernelGGL((KERN<false, true>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__);                 \
-    else hipLaunchKernelGGL((KERN<false, false>), grid, dim3(BLOCK), 0, stream, __VA_ARGS__);                         \
+    if (h->lanes == 16) LAUNCH16(KERN16, grid, stream, __VA_ARGS__);                                                  \
+    else LAUNCH4(KERN4, grid, stream, __VA_ARGS__);                                                                   \
   } while (0)
 
 #define CHECK_HANDLE(h)                                         \
@@ -2478,7 +2459,7 @@ extern "C" int etg_prepare_next_dynamics(EtgHandle* h, const float* dyn, const u
     }
   }
   hipStream_t s = (hipStream_t)stream;
-  const dim3 ge((h->N + 255) / 256), gc((4 * h->N + 255) / 256), g16((h->N + 3) / 4), g4(grid_for(h));
+  const dim3 ge((h->N + 255) / 256), gc((4 * h->N + 255) / 256);
   // a view of the robot arrays whose parameters are the NEXT rows, whose live state / ring are scratch (the robots keep running
   // on theirs) and whose settle cache is the real one: k_settle* leaves the settled state of the new rows in the cache
   DevState Dn = h->D;
@@ -2493,11 +2474,7 @@ extern "C" int etg_prepare_next_dynamics(EtgHandle* h, const float* dyn, const u
   mask = h->nx_mask;   // robots in the first RING ticks of their episode still read the cache's ring: not this time
   hipLaunchKernelGGL(k_set_params, dim3(grid_for(h)), dim3(BLOCK), 0, s, h->K, h->M, Dn, dyn, (const float*)nullptr,
                      (const float*)nullptr, 0, mask);   // (derives the rows; clears the scratch "cached" flag of the masked robots)
-  if (h->lanes == 16) {
-    LAUNCH16(k_settle16, g16, s, h->K, Dn, mask);
-  } else {
-    LAUNCH4(k_settle, g4, s, h->K, Dn, mask);
-  }
+  LAUNCH_TICK(k_settle16, k_settle, tick_grid(h), s, h->K, Dn, mask);
   hipLaunchKernelGGL(k_cache_sync, gc, dim3(256), 0, s, h->K, Dn, mask);      // scratch ring -> the cache's ring
   hipLaunchKernelGGL(k_fin_clear, ge, dim3(256), 0, s, h->K, h->D, mask);     // cached first observations: stale
   hipLaunchKernelGGL(k_next_flags, ge, dim3(256), 0, s, h->K, h->NX.ok, mask, (unsigned char)1);
@@ -2526,20 +2503,12 @@ extern "C" int etg_reset(EtgHandle* h, const uint8_t* mask, float* obs, void* st
   // 1. settle the masked robots that have no valid settle cache (kernel exits at once for the others)
   // 2. snapshot their ring / restore state + ring of the cached ones, mark everything masked as cached
   // 3. the part after the settle: control state, episode accumulators, first observation
-  const dim3 g16((h->N + 3) / 4), g4(grid_for(h)), gc((4 * h->N + 255) / 256), ge((h->N + 255) / 256);
+  const dim3 gc((4 * h->N + 255) / 256), ge((h->N + 255) / 256);
   hipStream_t s = (hipStream_t)stream;
-  if (h->lanes == 16) {
-    LAUNCH16(k_settle16, g16, s, h->K, h->D, mask);
-  } else {
-    LAUNCH4(k_settle, g4, s, h->K, h->D, mask);
-  }
+  LAUNCH_TICK(k_settle16, k_settle, tick_grid(h), s, h->K, h->D, mask);
   hipLaunchKernelGGL(k_cache_sync, gc, dim3(256), 0, s, h->K, h->D, mask);
   hipLaunchKernelGGL(k_cache_mark, ge, dim3(256), 0, s, h->K, h->D, mask);
-  if (h->lanes == 16) {
-    LAUNCH16(k_finish16, g16, s, h->K, h->D, mask, obs);
-  } else {
-    LAUNCH4(k_finish, g4, s, h->K, h->D, mask, obs);
-  }
+  LAUNCH_TICK(k_finish16, k_finish, tick_grid(h), s, h->K, h->D, mask, obs);
   hipLaunchKernelGGL(k_fin_store, ge, dim3(256), 0, s, h->K, h->D, mask, (const float*)obs);   // the clean row: before the noise
   launch_obs_noise(h, 1, mask, obs, s);
   if (mask && !h->all_cached) {   // did this masked reset settle the last robots without a cache?  (answer read by a later call)
@@ -2602,12 +2571,7 @@ extern "C" int etg_step(EtgHandle* h, const float* action, const uint8_t* donef,
   CHECK_HANDLE(h);
   if (int rc = step_checks(h, action, obs, reward, done)) return rc;
   advance_obs_stream(h, 1);
-  const dim3 g16((h->N + 3) / 4);
-  if (h->lanes == 16) {
-    LAUNCH16(k_step16, g16, (hipStream_t)stream, h->K, h->D, action, donef, obs, reward, done, info);
-  } else {
-    LAUNCH4(k_step, dim3(grid_for(h)), (hipStream_t)stream, h->K, h->D, action, donef, obs, reward, done, info);
-  }
+  LAUNCH_TICK(k_step16, k_step, tick_grid(h), (hipStream_t)stream, h->K, h->D, action, donef, obs, reward, done, info);
   launch_obs_noise(h, 1, nullptr, obs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return ETG_OK;
@@ -2631,11 +2595,7 @@ extern "C" int etg_step_range(EtgHandle* h, int env0, int count, const float* ac
   KCfg K = h->K;
   K.block0 = env0 / per_block;
   const dim3 grid((count + per_block - 1) / per_block);
-  if (h->lanes == 16) {
-    LAUNCH16(k_step16, grid, (hipStream_t)stream, K, h->D, action, donef, obs, reward, done, info);
-  } else {
-    LAUNCH4(k_step, grid, (hipStream_t)stream, K, h->D, action, donef, obs, reward, done, info);
-  }
+  LAUNCH_TICK(k_step16, k_step, grid, (hipStream_t)stream, K, h->D, action, donef, obs, reward, done, info);
   if (h->K.noise_on)
     hipLaunchKernelGGL(k_add_noise_range, dim3((16 * count + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->K, h->K.noise_call, env0, count, obs);
   HIP_TRY(hipGetLastError());
@@ -2661,11 +2621,7 @@ static int step_autoreset(EtgHandle* h, const float* action, const uint8_t* done
   // every robot has a cached settle: step and restart in ONE launch (k_step16_ar / k_step_ar)
   if (int rc = step_checks(h, action, obs, reward, done)) return rc;
   advance_obs_stream(h, 2);                     // two rows per robot at most: the step's (position c) and the reset's (c + 1)
-  if (h->lanes == 16) {
-    LAUNCH16(k_step16_ar, dim3((h->N + 3) / 4), s, h->K, h->D, action, donef, obs, reward, done, info, h->NX, T);
-  } else {
-    LAUNCH4(k_step_ar, dim3(grid_for(h)), s, h->K, h->D, action, donef, obs, reward, done, info, h->NX, T);
-  }
+  LAUNCH_TICK(k_step16_ar, k_step_ar, tick_grid(h), s, h->K, h->D, action, donef, obs, reward, done, info, h->NX, T);
   launch_obs_noise(h, 2, nullptr, T.obs, s, 0, /*back=*/1);         // the terminal rows: every robot's step row (position c)
   if (T.obs && h->lanes != 16) {   // (4 lanes: the step's rows went to T.obs only; those of the robots that go on move to obs)
     hipLaunchKernelGGL(k_term_rows, dim3((h->N * ETG_OBS_DIM + 255) / 256), dim3(256), 0, s, h->K, T.obs, done, obs);
@@ -2720,6 +2676,24 @@ extern "C" int etg_episode_stats(EtgHandle* h, float* ret, int32_t* len, void* s
   return ETG_OK;
 }
 
+// A rollout of n_steps control steps as fused launches of at most h->rollout_chunk steps: body(first_step, m) enqueues the launch
+// of the steps [first_step, first_step + m) and what follows it, once the sensor-noise stream has moved on by the m observations
+// per robot the launch writes.  A non-zero return of the body ends the rollout with that code.
+template <class Body> static inline int for_each_chunk(EtgHandle* h, int n_steps, Body&& body) {
+  for (int first_step = 0; first_step < n_steps; first_step += h->rollout_chunk) {
+    const int m = n_steps - first_step < h->rollout_chunk ? n_steps - first_step : h->rollout_chunk;
+    advance_obs_stream(h, m);
+    if (int rc = body(first_step, m)) return rc;
+  }
+  return ETG_OK;
+}
+// the end of a rollout call: launch errors, then the episode statistics if the caller asked for them
+static int rollout_end(EtgHandle* h, float* ret, int32_t* len, void* stream) {
+  HIP_TRY(hipGetLastError());
+  if (ret || len) return etg_episode_stats(h, ret, len, stream);
+  return ETG_OK;
+}
+
 // n_steps x env.step(action = 0) enqueued back-to-back on the stream (pretrain.py:129-154).
 // The same source as etg_step in another kernel: the compiler contracts multiply-adds differently in the two contexts, so the
 // two agree to rounding noise amplified by the contacts (joints ~1e-6 rad after one control step), not bit for bit.  The
@@ -2730,11 +2704,10 @@ extern "C" int etg_rollout_openloop(EtgHandle* h, int n_steps, float* obs, float
   if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_rollout_openloop: call etg_reset first");
   if (h->K.motor_mode != 2) {
     // fused: up to rollout_chunk control steps per launch, everything in registers in between
-    const int ROLLOUT_CHUNK = h->rollout_chunk;
-    const dim3 g16((h->N + 3) / 4), g4(grid_for(h));
+    const dim3 grid = tick_grid(h);
     hipStream_t s = (hipStream_t)stream;
     // per-wave cycle counters of this call's launches (etg_rollout_wave_cycles): one 8-byte store per wave and launch
-    const int n_launch = (n_steps + ROLLOUT_CHUNK - 1) / ROLLOUT_CHUNK, n_waves = (int)(h->lanes == 16 ? g16.x : g4.x);
+    const int n_launch = (n_steps + h->rollout_chunk - 1) / h->rollout_chunk, n_waves = (int)grid.x;
     if (h->wc_cap < n_launch * n_waves) {
       if (h->wave_cycles) (void)hipFree(h->wave_cycles);
       h->wave_cycles = nullptr;
@@ -2743,22 +2716,17 @@ extern "C" int etg_rollout_openloop(EtgHandle* h, int n_steps, float* obs, float
     }
     h->wc_launches = h->wave_cycles ? n_launch : 0;
     h->wc_waves = n_waves;
-    int launch = 0;
-    for (int done_steps = 0; done_steps < n_steps; done_steps += ROLLOUT_CHUNK, launch++) {
-      const int m = n_steps - done_steps < ROLLOUT_CHUNK ? n_steps - done_steps : ROLLOUT_CHUNK;
-      const bool last = done_steps + m == n_steps;
+    for_each_chunk(h, n_steps, [&](int first_step, int m) {
+      const int launch = first_step / h->rollout_chunk;
+      const bool last = first_step + m == n_steps;
       // stop_at_done: a robot's last row is written by the launch its episode ends in -- every launch writes to the caller's rows
       float* o = (obs && (last || h->K.stop_at_done)) ? obs : h->tmp_obs;
       long long* cyc = h->wave_cycles ? h->wave_cycles + (size_t)launch * n_waves : nullptr;
       const StatOut so = last ? StatOut{ret, (int*)len, cyc} : StatOut{nullptr, nullptr, cyc};
-      advance_obs_stream(h, m);
-      if (h->lanes == 16) {
-        LAUNCH16(k_rollout16, g16, s, h->K, h->D, m, o, so);
-      } else {
-        LAUNCH4(k_rollout, g4, s, h->K, h->D, m, o, so);
-      }
+      LAUNCH_TICK(k_rollout16, k_rollout, grid, s, h->K, h->D, m, o, so);
       if (o == obs) launch_rollout_noise(h, m, obs, s);
-    }
+      return ETG_OK;
+    });
     HIP_TRY(hipGetLastError());
     return ETG_OK;
   } else {
@@ -2779,31 +2747,77 @@ extern "C" int etg_rollout_actions(EtgHandle* h, const float* actions, int n_ste
   if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_rollout_actions: call etg_reset first");
   if (h->K.motor_mode == 2) return fail(ETG_ERR_STATE, "etg_rollout_actions: POSITION / TORQUE commands only ([n_steps,N,12] tapes)");
   if (h->K.noise_on && rec_obs) return fail(ETG_ERR_STATE, "etg_rollout_actions: per-step observations are recorded without sensor noise; switch it off");
-  const int ROLLOUT_CHUNK = h->rollout_chunk;
-  const dim3 g16((h->N + 3) / 4), g4(grid_for(h));
   hipStream_t s = (hipStream_t)stream;
   const size_t N = h->N;
-  for (int d0 = 0; d0 < n_steps; d0 += ROLLOUT_CHUNK) {
-    const int m = n_steps - d0 < ROLLOUT_CHUNK ? n_steps - d0 : ROLLOUT_CHUNK;
-    advance_obs_stream(h, m);
+  const int rc = for_each_chunk(h, n_steps, [&](int d0, int m) -> int {
     const TapeOut T = {rec_joint_angle ? rec_joint_angle + (size_t)d0 * N * ETG_ACT_DIM : nullptr, rec_imu ? rec_imu + (size_t)d0 * N * 6 : nullptr,
                        rec_obs ? rec_obs + (size_t)d0 * N * ETG_OBS_DIM : nullptr, rec_reward ? rec_reward + (size_t)d0 * N : nullptr,
                        rec_done ? rec_done + (size_t)d0 * N : nullptr};
     const float* a = actions + (size_t)d0 * N * ETG_ACT_DIM;
-    if (h->lanes == 16) {
-      LAUNCH16(k_rollout_actions16, g16, s, h->K, h->D, m, a, obs, T);
-    } else {
-      LAUNCH4(k_rollout_actions, g4, s, h->K, h->D, m, a, obs, T);
-    }
+    LAUNCH_TICK(k_rollout_actions16, k_rollout_actions, tick_grid(h), s, h->K, h->D, m, a, obs, T);
     launch_rollout_noise(h, m, obs, s);
     // the last step of EVERY launch writes its row to `obs`, not to the tape: the tape gets its copy per chunk (rows 49, 99,
     // ... and n_steps - 1; recorded observations carry no sensor noise, which the check above enforces)
     if (rec_obs)
       HIP_TRY(hipMemcpyAsync(rec_obs + (size_t)(d0 + m - 1) * N * ETG_OBS_DIM, obs, N * ETG_OBS_DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
-  }
-  HIP_TRY(hipGetLastError());
-  if (ret || len) return etg_episode_stats(h, ret, len, stream);
+    return ETG_OK;
+  });
+  if (rc) return rc;
+  return rollout_end(h, ret, len, stream);
+}
+
+// ---- the closed-loop entry points (etg_rollout_policy, etg_rollout_policy_record, etg_step_policy): what they ask of the
+// policy, and the two forms its weights are handed to the kernels in.  fn: the entry point's name for the error text
+static int policy_checks(const char* fn, const EtgHandle* h, const EtgPolicy* pol, int obs_col0) {
+  if (pol->device != h->device) return fail(ETG_ERR_BAD_ARG, std::string(fn) + ": policy and simulator live on different devices");
+  if (obs_col0 < 0 || obs_col0 + pol->in_dim > ETG_OBS_DIM || pol->out_dim != ETG_ACT_DIM)
+    return fail(ETG_ERR_BAD_ARG, std::string(fn) + ": the policy must map observation columns [col0, col0 + in_dim) to 12 actions");
   return ETG_OK;
+}
+// the 16-robot tile's fragments (the bf16 kernels read the bf16 copies packed at load time)
+static PolicyW policy_tile(const EtgPolicy* pol, bool bf, int obs_col0) {
+  return {(const float4*)(bf ? pol->w1h : pol->w1), (const float4*)(bf ? pol->w2h : pol->w2), (const float4*)(bf ? pol->w3h : pol->w3),
+          pol->b1, pol->b2, pol->b3, pol->in_dim, pol->out_dim, obs_col0};
+}
+// the per-wave kernels' streams (PolicyW: w1 = both hidden layers, w2 unused)
+static PolicyW policy_wave(const EtgPolicy* pol, int obs_col0) {
+  return {(const float4*)pol->w12q, nullptr, (const float4*)pol->w3q, pol->b1, pol->b2, pol->b3, pol->in_dim, pol->out_dim, obs_col0};
+}
+
+// The closed-loop rollout on the 16-lane mapping, for etg_rollout_policy (rec == nullptr) and etg_rollout_policy_record (rec: the
+// [n_steps][N][...] arrays of the whole rollout; the _rec kernels get each chunk's part of them and the log-std head).
+// precision 0: one wave per workgroup, the policy tile per wave (k_rollout_policy16w: no workgroup barrier); precision 1 (bf16
+// operands, an opt-in arithmetic): the 16-robot tile of 4 waves (k_rollout_policy16)
+static int rollout_policy16(EtgHandle* h, EtgPolicy* pol, int n_steps, float act_scale, int precision, int obs_col0, float* obs,
+                            const RecOut* rec, float* ret, int32_t* len, void* stream) {
+  const bool bf = precision != 0;
+  const bool per_wave = precision == 0 && pol->in_dim <= 4 * pol::KQ1 && pol->out_dim <= 12;
+  const PolicyW P = per_wave ? policy_wave(pol, obs_col0) : policy_tile(pol, bf, obs_col0);
+  const dim3 g = per_wave ? dim3(h->N / 4) : dim3(h->N / 16), b = per_wave ? dim3(BLOCK) : dim3(256);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t N = h->N;
+  for_each_chunk(h, n_steps, [&](int d0, int m) {
+    RecOut R = {};
+    if (rec)
+      R = {rec->obs + (size_t)d0 * N * ETG_OBS_DIM, rec->act + (size_t)d0 * N * ETG_ACT_DIM, rec->rew + (size_t)d0 * N, rec->done + (size_t)d0 * N,
+           rec->noise ? rec->noise + (size_t)d0 * N * ETG_ACT_DIM : nullptr,
+           (const float4*)(per_wave ? pol->w3sq : (bf ? pol->w3sh : pol->w3s)), pol->b3s};
+    dispatch16(h->K, [&](auto f_, auto k_, auto p_) {
+      constexpr bool F = ETG_V(f_), KN = ETG_V(k_), PL = ETG_V(p_);
+      if (rec) {
+        if (per_wave) hipLaunchKernelGGL((k_rollout_policy16w_rec<F, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs, R);
+        else if (!bf) hipLaunchKernelGGL((k_rollout_policy16_rec<F, false, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs, R);
+        else hipLaunchKernelGGL((k_rollout_policy16_rec<F, true, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs, R);
+      } else {
+        if (per_wave) hipLaunchKernelGGL((k_rollout_policy16w<F, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs);
+        else if (!bf) hipLaunchKernelGGL((k_rollout_policy16<F, false, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs);
+        else hipLaunchKernelGGL((k_rollout_policy16<F, true, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs);
+      }
+    });
+    launch_rollout_noise(h, m, obs, s);   // every chunk ends in the caller's rows: the next chunk reads them
+    return ETG_OK;
+  });
+  return rollout_end(h, ret, len, stream);
 }
 
 extern "C" int etg_rollout_policy(EtgHandle* h, EtgPolicy* pol, int n_steps, float act_scale, int precision, int obs_col0,
@@ -2811,65 +2825,31 @@ extern "C" int etg_rollout_policy(EtgHandle* h, EtgPolicy* pol, int n_steps, flo
   CHECK_HANDLE(h);
   if (!pol || n_steps <= 0 || !obs) return fail(ETG_ERR_BAD_ARG, "etg_rollout_policy: bad arguments");
   if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_rollout_policy: call etg_reset first");
-  if (pol->device != h->device) return fail(ETG_ERR_BAD_ARG, "etg_rollout_policy: policy and simulator live on different devices");
-  if (obs_col0 < 0 || obs_col0 + pol->in_dim > ETG_OBS_DIM || pol->out_dim != ETG_ACT_DIM)
-    return fail(ETG_ERR_BAD_ARG, "etg_rollout_policy: the policy must map observation columns [col0, col0 + in_dim) to 12 actions");
+  if (int rc = policy_checks("etg_rollout_policy", h, pol, obs_col0)) return rc;
   if (h->K.motor_mode == 2 || (h->lanes == 16 ? h->N % 16 != 0 : h->N % 64 != 0))
     return fail(ETG_ERR_STATE, "etg_rollout_policy: needs POSITION/TORQUE mode and whole workgroups: num_envs % 16 == 0 on the 16-lane "
                                "mapping (16 robots per workgroup), num_envs % 64 == 0 on the 4-lane one (64 per workgroup)");
-  const bool bf = precision != 0;   // the bf16 kernels read the bf16 fragments packed at load time
-  PolicyW P = {(const float4*)(bf ? pol->w1h : pol->w1), (const float4*)(bf ? pol->w2h : pol->w2), (const float4*)(bf ? pol->w3h : pol->w3), pol->b1, pol->b2, pol->b3,
-               pol->in_dim, pol->out_dim, obs_col0};
-  const int ROLLOUT_CHUNK = h->rollout_chunk;
-  const dim3 g(h->N / 16), b(256);
+  if (h->lanes == 16) return rollout_policy16(h, pol, n_steps, act_scale, precision, obs_col0, obs, nullptr, ret, len, stream);
+  // the 4-lane mapping: 64 robots per workgroup, two stacked policy tiles per pass (k_rollout_policy4)
+  const bool bf = precision != 0;
+  const PolicyW P = policy_tile(pol, bf, obs_col0);
+  const dim3 g4(h->N / 64), b(256);
   hipStream_t s = (hipStream_t)stream;
-  const bool flat = h->K.terrain == 0;
-  if (h->lanes == 4) {   // the 4-lane mapping: 64 robots per workgroup, two stacked policy tiles per pass (k_rollout_policy4)
-    const dim3 g4(h->N / 64);
-    const bool pl = plain_config(h->K);
-    for (int done_steps = 0; done_steps < n_steps; done_steps += ROLLOUT_CHUNK) {
-      const int m = n_steps - done_steps < ROLLOUT_CHUNK ? n_steps - done_steps : ROLLOUT_CHUNK;
-      advance_obs_stream(h, m);
-#define LAUNCH_POLICY4(F_, P_, K_)                                                                                    \
-  do {                                                                                                                \
-    if (precision == 0) hipLaunchKernelGGL((k_rollout_policy4<F_, false, P_, K_>), g4, b, 0, s, h->K, h->D, P, m, act_scale, obs); \
-    else hipLaunchKernelGGL((k_rollout_policy4<F_, true, P_, K_>), g4, b, 0, s, h->K, h->D, P, m, act_scale, obs);    \
-  } while (0)
-      if (h->K.knee == 3)   // (the closed-loop kernel is not instantiated with three body rows per leg: callers step instead)
-        return fail(ETG_ERR_STATE, "etg_rollout_policy: body_contacts = 3 is served by etg_step / etg_rollout_openloop / etg_rollout_actions");
-      if (h->K.knee && flat) LAUNCH_POLICY4(true, false, 1);
-      else if (h->K.knee) LAUNCH_POLICY4(false, false, 1);
-      else if (flat && pl) LAUNCH_POLICY4(true, true, 0);
-      else if (flat) LAUNCH_POLICY4(true, false, 0);
-      else if (pl) LAUNCH_POLICY4(false, true, 0);
-      else LAUNCH_POLICY4(false, false, 0);
-#undef LAUNCH_POLICY4
-      launch_rollout_noise(h, m, obs, s);
-    }
-    HIP_TRY(hipGetLastError());
-    if (ret || len) return etg_episode_stats(h, ret, len, stream);
-    return ETG_OK;
-  }
-  // precision 0: one wave per workgroup, the policy tile per wave (k_rollout_policy16w: no workgroup barrier); precision 1 (bf16
-  // operands, an opt-in arithmetic): the 16-robot tile of 4 waves (k_rollout_policy16)
-  const bool per_wave = precision == 0 && pol->in_dim <= 4 * pol::KQ1 && pol->out_dim <= 12;
-  const PolicyW Pq = {(const float4*)pol->w12q, nullptr, (const float4*)pol->w3q, pol->b1, pol->b2, pol->b3, pol->in_dim, pol->out_dim, obs_col0};
-  for (int done_steps = 0; done_steps < n_steps; done_steps += ROLLOUT_CHUNK) {
-    const int m = n_steps - done_steps < ROLLOUT_CHUNK ? n_steps - done_steps : ROLLOUT_CHUNK;
-    advance_obs_stream(h, m);
-#define LAUNCH_POLICY16(F_, K_, P_)                                                                                   \
-  do {                                                                                                                \
-    if (per_wave) hipLaunchKernelGGL((k_rollout_policy16w<F_, K_, P_>), dim3(h->N / 4), dim3(BLOCK), 0, s, h->K, h->D, Pq, m, act_scale, obs); \
-    else if (precision == 0) hipLaunchKernelGGL((k_rollout_policy16<F_, false, K_, P_>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs); \
-    else hipLaunchKernelGGL((k_rollout_policy16<F_, true, K_, P_>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs);    \
-  } while (0)
-    DISPATCH16(LAUNCH_POLICY16);
-#undef LAUNCH_POLICY16
-    launch_rollout_noise(h, m, obs, s);   // every chunk ends in the caller's rows: the next chunk reads them
-  }
-  HIP_TRY(hipGetLastError());
-  if (ret || len) return etg_episode_stats(h, ret, len, stream);
-  return ETG_OK;
+  const int rc = for_each_chunk(h, n_steps, [&](int, int m) {
+    int refused = ETG_OK;
+    dispatch4(h->K, [&](auto f_, auto p_, auto b_) {
+      constexpr bool F = ETG_V(f_), PL = ETG_V(p_);
+      constexpr int BODY = ETG_V(b_);
+      if constexpr (BODY == 3)   // (the closed-loop kernel is not instantiated with three body rows per leg: callers step instead)
+        refused = fail(ETG_ERR_STATE, "etg_rollout_policy: body_contacts = 3 is served by etg_step / etg_rollout_openloop / etg_rollout_actions");
+      else if (!bf) hipLaunchKernelGGL((k_rollout_policy4<F, false, PL, BODY>), g4, b, 0, s, h->K, h->D, P, m, act_scale, obs);
+      else hipLaunchKernelGGL((k_rollout_policy4<F, true, PL, BODY>), g4, b, 0, s, h->K, h->D, P, m, act_scale, obs);
+    });
+    if (!refused) launch_rollout_noise(h, m, obs, s);
+    return refused;
+  });
+  if (rc) return rc;
+  return rollout_end(h, ret, len, stream);
 }
 
 extern "C" int etg_rollout_policy_record(EtgHandle* h, EtgPolicy* pol, int n_steps, float act_scale, int precision, int obs_col0,
@@ -2880,41 +2860,11 @@ extern "C" int etg_rollout_policy_record(EtgHandle* h, EtgPolicy* pol, int n_ste
     return fail(ETG_ERR_BAD_ARG, "etg_rollout_policy_record: bad arguments");
   if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_rollout_policy_record: call etg_reset first");
   if (noise && !pol->has_std) return fail(ETG_ERR_STATE, "etg_rollout_policy_record: a stochastic rollout needs etg_policy_load_std() first");
-  if (pol->device != h->device) return fail(ETG_ERR_BAD_ARG, "etg_rollout_policy_record: policy and simulator live on different devices");
-  if (obs_col0 < 0 || obs_col0 + pol->in_dim > ETG_OBS_DIM || pol->out_dim != ETG_ACT_DIM)
-    return fail(ETG_ERR_BAD_ARG, "etg_rollout_policy_record: the policy must map observation columns [col0, col0 + in_dim) to 12 actions");
+  if (int rc = policy_checks("etg_rollout_policy_record", h, pol, obs_col0)) return rc;
   if (h->lanes != 16 || h->N % 16 != 0 || h->K.motor_mode == 2)
     return fail(ETG_ERR_STATE, "etg_rollout_policy_record: needs the 16-lanes-per-robot mapping, num_envs % 16 == 0, POSITION/TORQUE mode");
-  const bool bf = precision != 0;   // the bf16 kernels read the bf16 fragments packed at load time
-  PolicyW P = {(const float4*)(bf ? pol->w1h : pol->w1), (const float4*)(bf ? pol->w2h : pol->w2), (const float4*)(bf ? pol->w3h : pol->w3), pol->b1, pol->b2, pol->b3,
-               pol->in_dim, pol->out_dim, obs_col0};
-  const int ROLLOUT_CHUNK = h->rollout_chunk;
-  const dim3 g(h->N / 16), b(256);
-  hipStream_t s = (hipStream_t)stream;
-  const bool flat = h->K.terrain == 0;
-  const size_t N = h->N;
-  for (int done_steps = 0; done_steps < n_steps; done_steps += ROLLOUT_CHUNK) {
-    const int m = n_steps - done_steps < ROLLOUT_CHUNK ? n_steps - done_steps : ROLLOUT_CHUNK;
-    advance_obs_stream(h, m);
-    const bool per_wave = precision == 0 && pol->in_dim <= 4 * pol::KQ1 && pol->out_dim <= 12;
-    const RecOut R = {rec_obs + (size_t)done_steps * N * ETG_OBS_DIM, rec_act + (size_t)done_steps * N * ETG_ACT_DIM,
-                      rec_reward + (size_t)done_steps * N, rec_done + (size_t)done_steps * N,
-                      noise ? noise + (size_t)done_steps * N * ETG_ACT_DIM : nullptr,
-                      (const float4*)(per_wave ? pol->w3sq : (bf ? pol->w3sh : pol->w3s)), pol->b3s};
-    const PolicyW Pq = {(const float4*)pol->w12q, nullptr, (const float4*)pol->w3q, pol->b1, pol->b2, pol->b3, pol->in_dim, pol->out_dim, obs_col0};
-#define LAUNCH_POLICY16R(F_, K_, P_)                                                                                  \
-  do {                                                                                                                \
-    if (per_wave) hipLaunchKernelGGL((k_rollout_policy16w_rec<F_, K_, P_>), dim3(h->N / 4), dim3(BLOCK), 0, s, h->K, h->D, Pq, m, act_scale, obs, R); \
-    else if (precision == 0) hipLaunchKernelGGL((k_rollout_policy16_rec<F_, false, K_, P_>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs, R); \
-    else hipLaunchKernelGGL((k_rollout_policy16_rec<F_, true, K_, P_>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs, R);    \
-  } while (0)
-    DISPATCH16(LAUNCH_POLICY16R);
-#undef LAUNCH_POLICY16R
-    launch_rollout_noise(h, m, obs, s);   // every chunk ends in the caller's rows: the next chunk reads them
-  }
-  HIP_TRY(hipGetLastError());
-  if (ret || len) return etg_episode_stats(h, ret, len, stream);
-  return ETG_OK;
+  const RecOut rec = {rec_obs, rec_act, rec_reward, rec_done, noise, nullptr, nullptr};
+  return rollout_policy16(h, pol, n_steps, act_scale, precision, obs_col0, obs, &rec, ret, len, stream);
 }
 
 // One closed-loop control step of every robot (include/etgsim_step_policy.h): k_step_policy16 / k_step_policy16_ar, one launch
@@ -2927,9 +2877,7 @@ extern "C" int etg_step_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, in
     return fail(ETG_ERR_BAD_ARG, "etg_step_policy: policy, obs, terminal_obs, reward and done must be non-null");
   if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_step_policy: call etg_reset first");
   if (noise && !pol->has_std) return fail(ETG_ERR_STATE, "etg_step_policy: sampling needs etg_policy_load_std() first");
-  if (pol->device != h->device) return fail(ETG_ERR_BAD_ARG, "etg_step_policy: policy and simulator live on different devices");
-  if (obs_col0 < 0 || obs_col0 + pol->in_dim > ETG_OBS_DIM || pol->out_dim != ETG_ACT_DIM)
-    return fail(ETG_ERR_BAD_ARG, "etg_step_policy: the policy must map observation columns [col0, col0 + in_dim) to 12 actions");
+  if (int rc = policy_checks("etg_step_policy", h, pol, obs_col0)) return rc;
   if (precision != 0 || pol->in_dim > 4 * pol::KQ1)
     return fail(ETG_ERR_BAD_ARG, "etg_step_policy: the kernel runs the fp32 per-wave actor tile: precision 0, in_dim <= 64");
   if (h->lanes != 16 || h->N % 16 != 0)
@@ -2939,7 +2887,7 @@ extern "C" int etg_step_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, in
   if (auto_reset) refresh_all_cached(h);
   const bool fused_reset = auto_reset && h->all_cached;
   advance_obs_stream(h, fused_reset ? 2 : 1);
-  const PolicyW Pq = {(const float4*)pol->w12q, nullptr, (const float4*)pol->w3q, pol->b1, pol->b2, pol->b3, pol->in_dim, pol->out_dim, obs_col0};
+  const PolicyW Pq = policy_wave(pol, obs_col0);
   const StepPolOut O = {noise, (const float4*)pol->w3sq, pol->b3s, donef, act, act_obs, terminal_obs, reward, done, info};
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(h->N / 4);

@@ -15,6 +15,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/etgsim.h"
 
 #if defined(__HIPCC__)
@@ -102,6 +104,44 @@ struct KCfg {
 inline bool plain_config(const KCfg& K) {
   return K.motor_mode == 0 && !K.enable_filter && !K.enable_interp && !(K.torque_limit > 0.0f) && !(K.clip_cmd > 0.0f) &&
          !K.ext_force && K.knee != 3 && K.etg_on && !K.fric_pyramid && K.pd_n < 0 && !(K.restitution > 0.0f) && !K.strength_on;   // (joint limits: in every instantiation)
+}
+
+// ---- the compile-time variants of the step / reset / rollout kernels and the choice among them (host only).  The kernel
+// launches (LAUNCH16 / LAUNCH4 in etg_kernels.hip) and the test emulation (tests/emu/etg_emu.cpp) both go through dispatch16 /
+// dispatch4, so a configuration runs the same variant in both; tests/test_variant_choice.py pins the choice.
+// 16 lanes per robot, <FLAT, KNEE, PLAIN>: {flat ground, heightfield} x {plain robot layer + body rows (the default), plain
+// robot layer with toe spheres only, all options + body rows}.
+#define ETG_VARIANTS16(X) \
+  X(true, true, true) X(true, false, true) X(true, true, false) X(false, true, true) X(false, false, true) X(false, true, false)
+// 4 lanes per robot, <FLAT, PLAIN, BODY>: {flat ground, heightfield} x {all options + 3 body rows per leg, all options + 1 body
+// row, plain robot layer, all options}.
+#define ETG_VARIANTS4(X)                                                                          \
+  X(true, false, 3) X(false, false, 3) X(true, false, 1) X(false, false, 1) X(true, true, 0) X(true, false, 0) \
+  X(false, true, 0) X(false, false, 0)
+
+// calls f(FLAT, KNEE, PLAIN) with the variant's tuple as std::integral_constants.  The all-options variant also serves
+// body_contacts = 0 of the all-options layer (the rows are switched off at run time: KCfg.knee == 0), so a configuration that
+// is not plain runs <FLAT, true, false> whatever K.knee is and a kernel has six instantiations, not eight.
+template <class Fn> inline void dispatch16(const KCfg& K, Fn&& f) {
+  const bool flat = K.terrain == 0, plain = plain_config(K), knee = !plain || K.knee != 0;
+#define ETG_X(F_, K_, P_) \
+  if (flat == F_ && knee == K_ && plain == P_) return f(std::integral_constant<bool, F_>{}, std::integral_constant<bool, K_>{}, std::integral_constant<bool, P_>{});
+  ETG_VARIANTS16(ETG_X)
+#undef ETG_X
+}
+// calls f(FLAT, PLAIN, BODY).  A plain robot layer WITH body rows (the default configuration beyond 8192 robots) runs the
+// all-options instantiation: the PLAIN specialisation is worth ~3 % where the tick fits the register file, but the 4-lane tick
+// with body rows is at the 512-register budget with 528-544 B of scratch either way (profiles/r06_isa_baseline.json:
+// k_rollout<flat, all options, 1>), its time is the spills' and the sweeps', and every further instantiation of it costs ~70 s of
+// build for the six 4-lane kernels.
+template <class Fn> inline void dispatch4(const KCfg& K, Fn&& f) {
+  const bool flat = K.terrain == 0;
+  const int body = K.knee == 3 ? 3 : K.knee ? 1 : 0;
+  const bool plain = body == 0 && plain_config(K);
+#define ETG_X(F_, P_, B_) \
+  if (flat == F_ && plain == P_ && body == B_) return f(std::integral_constant<bool, F_>{}, std::integral_constant<bool, P_>{}, std::integral_constant<int, B_>{});
+  ETG_VARIANTS4(ETG_X)
+#undef ETG_X
 }
 
 // counter-based standard normal pair for (seed, robot, observation index, channel): splitmix64 finaliser twice, then

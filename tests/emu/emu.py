@@ -147,6 +147,13 @@ class EmuSim:
         (16-lane mapping); process-wide"""
         lib().emu_set_force_body(int(bool(on)))
 
+    def variant(self):
+        """the kernel variant dispatch16 / dispatch4 (etg_layout.h) pick for this configuration, as the launches do:
+        (FLAT, KNEE, PLAIN) on 16 lanes, (FLAT, PLAIN, BODY) on 4"""
+        out = (C.c_int * 3)()
+        self._l.emu_variant(self._h, out)
+        return tuple(out)
+
     def replication_check(self, env=0, nticks=50):
         f = self._l.emu16_tick_replication_check if self.lanes == 16 else self._l.emu_tick_replication_check
         return f(self._h, int(env), int(nticks))

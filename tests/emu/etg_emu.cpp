@@ -278,6 +278,17 @@ struct Emu {
 
 using namespace etg;
 
+// the context of a robot is EmuCtx16T / EmuCtxT built from the tuple dispatch16 / dispatch4 (etg_layout.h) hand over: the
+// choice of the variant is the kernel launches' own code
+#define ETG_V(c) decltype(c)::value
+// the tuple the handle's configuration runs: (FLAT, KNEE, PLAIN) on 16 lanes, (FLAT, PLAIN, BODY) on 4 (tests/test_variant_choice.py)
+extern "C" void emu_variant(void* h, int* out) {
+  Emu* e = (Emu*)h;
+  auto put = [&](auto a, auto b, auto c) { out[0] = ETG_V(a); out[1] = ETG_V(b); out[2] = ETG_V(c); };
+  if (e->lanes == 16) dispatch16(e->K, put);
+  else dispatch4(e->K, put);
+}
+
 extern "C" void* emu_create(const EtgConfig* cfg, const EtgRobotModel* model) {
   Emu* e = new Emu();
   e->K = make_kcfg(*cfg, *model);
@@ -383,26 +394,10 @@ extern "C" void emu_reset(void* h, const uint8_t* mask, float* obs) {
   for (int i = 0; i < e->N; i++) {
     if (mask && !mask[i]) continue;
     const float ox = e->reset_off.empty() ? 0.0f : e->reset_off[2 * i], oy = e->reset_off.empty() ? 0.0f : e->reset_off[2 * i + 1];
-    if (e->lanes == 16) {
-      const bool pl = plain_config(e->K);                       // same instantiation choice as LAUNCH16 in etg_kernels.hip
-      const bool kn = e->K.knee != 0, fl = e->K.terrain == 0;   // (DISPATCH16)
-      if (fl && pl && kn) emu_reset16<EmuCtx16T<true, true, true>>(e, i, obs, ox, oy);
-      else if (fl && pl) emu_reset16<EmuCtx16T<true, false, true>>(e, i, obs, ox, oy);
-      else if (fl) emu_reset16<EmuCtx16T<true, true, false>>(e, i, obs, ox, oy);
-      else if (pl && kn) emu_reset16<EmuCtx16T<false, true, true>>(e, i, obs, ox, oy);
-      else if (pl) emu_reset16<EmuCtx16T<false, false, true>>(e, i, obs, ox, oy);
-      else emu_reset16<EmuCtx16T<false, true, false>>(e, i, obs, ox, oy);
-      continue;
-    }
-    const bool pl4 = plain_config(e->K);                        // same choice as LAUNCH4 in etg_kernels.hip
-    if (e->K.knee == 3 && e->K.terrain == 0) emu_reset4<EmuCtxT<true, false, 3>>(e, i, obs, ox, oy);
-    else if (e->K.knee == 3) emu_reset4<EmuCtxT<false, false, 3>>(e, i, obs, ox, oy);
-    else if (e->K.knee && e->K.terrain == 0) emu_reset4<EmuCtxT<true, false, 1>>(e, i, obs, ox, oy);
-    else if (e->K.knee) emu_reset4<EmuCtxT<false, false, 1>>(e, i, obs, ox, oy);
-    else if (e->K.terrain == 0 && pl4) emu_reset4<EmuCtxT<true, true>>(e, i, obs, ox, oy);
-    else if (e->K.terrain == 0) emu_reset4<EmuCtxT<true>>(e, i, obs, ox, oy);
-    else if (pl4) emu_reset4<EmuCtxT<false, true>>(e, i, obs, ox, oy);
-    else emu_reset4<EmuCtxT<false>>(e, i, obs, ox, oy);
+    if (e->lanes == 16)
+      dispatch16(e->K, [&](auto f, auto k, auto p) { emu_reset16<EmuCtx16T<ETG_V(f), ETG_V(k), ETG_V(p)>>(e, i, obs, ox, oy); });
+    else
+      dispatch4(e->K, [&](auto f, auto p, auto b) { emu_reset4<EmuCtxT<ETG_V(f), ETG_V(p), ETG_V(b)>>(e, i, obs, ox, oy); });
   }
   emu_obs_noise(e, mask, obs);
 }
@@ -413,14 +408,7 @@ extern "C" void emu_step(void* h, const float* action, const uint8_t* donef, flo
     if (e->lanes == 16) {
       F16 r16, d16;
       F16 dn(donef ? (float)donef[i] : 0.f);
-      const bool pl = plain_config(e->K);
-      const bool kn = e->K.knee != 0, fl = e->K.terrain == 0;   // (DISPATCH16)
-      if (fl && pl && kn) emu_step16<EmuCtx16T<true, true, true>>(e, i, action, dn, obs, r16, d16, info);
-      else if (fl && pl) emu_step16<EmuCtx16T<true, false, true>>(e, i, action, dn, obs, r16, d16, info);
-      else if (fl) emu_step16<EmuCtx16T<true, true, false>>(e, i, action, dn, obs, r16, d16, info);
-      else if (pl && kn) emu_step16<EmuCtx16T<false, true, true>>(e, i, action, dn, obs, r16, d16, info);
-      else if (pl) emu_step16<EmuCtx16T<false, false, true>>(e, i, action, dn, obs, r16, d16, info);
-      else emu_step16<EmuCtx16T<false, true, false>>(e, i, action, dn, obs, r16, d16, info);
+      dispatch16(e->K, [&](auto f, auto k, auto p) { emu_step16<EmuCtx16T<ETG_V(f), ETG_V(k), ETG_V(p)>>(e, i, action, dn, obs, r16, d16, info); });
       reward[i] = r16.v[0];
       done[i] = d16.v[0] > 0.5f;
       continue;
@@ -435,15 +423,7 @@ extern "C" void emu_step(void* h, const float* action, const uint8_t* donef, flo
     }
     F4 r, d;
     const F4 dn4(donef ? (float)donef[i] : 0.f);
-    const bool pl4 = plain_config(e->K);
-    if (e->K.knee == 3 && e->K.terrain == 0) emu_step4<EmuCtxT<true, false, 3>>(e, i, L, act, dn4, obs, r, d, info, hybrid ? hyb : nullptr);
-    else if (e->K.knee == 3) emu_step4<EmuCtxT<false, false, 3>>(e, i, L, act, dn4, obs, r, d, info, hybrid ? hyb : nullptr);
-    else if (e->K.knee && e->K.terrain == 0) emu_step4<EmuCtxT<true, false, 1>>(e, i, L, act, dn4, obs, r, d, info, hybrid ? hyb : nullptr);
-    else if (e->K.knee) emu_step4<EmuCtxT<false, false, 1>>(e, i, L, act, dn4, obs, r, d, info, hybrid ? hyb : nullptr);
-    else if (e->K.terrain == 0 && pl4) emu_step4<EmuCtxT<true, true>>(e, i, L, act, dn4, obs, r, d, info, hybrid ? hyb : nullptr);
-    else if (e->K.terrain == 0) emu_step4<EmuCtxT<true>>(e, i, L, act, dn4, obs, r, d, info, hybrid ? hyb : nullptr);
-    else if (pl4) emu_step4<EmuCtxT<false, true>>(e, i, L, act, dn4, obs, r, d, info, hybrid ? hyb : nullptr);
-    else emu_step4<EmuCtxT<false>>(e, i, L, act, dn4, obs, r, d, info, hybrid ? hyb : nullptr);
+    dispatch4(e->K, [&](auto f, auto p, auto b) { emu_step4<EmuCtxT<ETG_V(f), ETG_V(p), ETG_V(b)>>(e, i, L, act, dn4, obs, r, d, info, hybrid ? hyb : nullptr); });
     store_state(c0, e->base.data(), e->leg.data(), L);
     reward[i] = r.v[0];
     done[i] = d.v[0] > 0.5f;
@@ -469,26 +449,10 @@ extern "C" void emu_rollout_openloop(void* h, int n_steps, int stop_at_done, flo
   e->K.noise_call = e->obs_calls;
   e->obs_calls += (unsigned)n_steps;
   for (int i = 0; i < e->N; i++) {
-    if (e->lanes == 16) {
-      const bool pl = plain_config(e->K);
-      const bool kn = e->K.knee != 0, fl = e->K.terrain == 0;   // (DISPATCH16)
-      if (fl && pl && kn) emu_rollout16<EmuCtx16T<true, true, true>>(e, i, n_steps, obs);
-      else if (fl && pl) emu_rollout16<EmuCtx16T<true, false, true>>(e, i, n_steps, obs);
-      else if (fl) emu_rollout16<EmuCtx16T<true, true, false>>(e, i, n_steps, obs);
-      else if (pl && kn) emu_rollout16<EmuCtx16T<false, true, true>>(e, i, n_steps, obs);
-      else if (pl) emu_rollout16<EmuCtx16T<false, false, true>>(e, i, n_steps, obs);
-      else emu_rollout16<EmuCtx16T<false, true, false>>(e, i, n_steps, obs);
-    } else {
-      const bool pl4 = plain_config(e->K);                        // (LAUNCH4)
-      if (e->K.knee == 3 && e->K.terrain == 0) emu_rollout4<EmuCtxT<true, false, 3>>(e, i, n_steps, obs);
-      else if (e->K.knee == 3) emu_rollout4<EmuCtxT<false, false, 3>>(e, i, n_steps, obs);
-      else if (e->K.knee && e->K.terrain == 0) emu_rollout4<EmuCtxT<true, false, 1>>(e, i, n_steps, obs);
-      else if (e->K.knee) emu_rollout4<EmuCtxT<false, false, 1>>(e, i, n_steps, obs);
-      else if (e->K.terrain == 0 && pl4) emu_rollout4<EmuCtxT<true, true>>(e, i, n_steps, obs);
-      else if (e->K.terrain == 0) emu_rollout4<EmuCtxT<true>>(e, i, n_steps, obs);
-      else if (pl4) emu_rollout4<EmuCtxT<false, true>>(e, i, n_steps, obs);
-      else emu_rollout4<EmuCtxT<false>>(e, i, n_steps, obs);
-    }
+    if (e->lanes == 16)
+      dispatch16(e->K, [&](auto f, auto k, auto p) { emu_rollout16<EmuCtx16T<ETG_V(f), ETG_V(k), ETG_V(p)>>(e, i, n_steps, obs); });
+    else
+      dispatch4(e->K, [&](auto f, auto p, auto b) { emu_rollout4<EmuCtxT<ETG_V(f), ETG_V(p), ETG_V(b)>>(e, i, n_steps, obs); });
     if (ret) ret[i] = e->ctl[(size_t)CT_RET * e->N + i];
     if (len) len[i] = (int)e->ctl[(size_t)CT_LEN * e->N + i];
   }
