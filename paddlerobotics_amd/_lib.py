@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h, include/etgsim_terminal.h,
-include/etgsim_render.h and include/etgsim_sac.h (paddlerobotics_amd/csrc/libetgsim.so).
+include/etgsim_render.h, include/etgsim_sac.h and include/etgsim_bc.h (paddlerobotics_amd/csrc/libetgsim.so).
 
 There is no CPU fallback: if the library is missing this module raises, and if no HIP
 device is visible etg_create() fails with ETG_ERR_NO_DEVICE.
@@ -30,6 +30,9 @@ RENDER_SYMBOLS = ["etg_render"]
 # ... and include/etgsim_sac.h
 SAC_SYMBOLS = ["etg_sac_create", "etg_sac_destroy", "etg_sac_set_hyper", "etg_sac_load", "etg_sac_store", "etg_sac_load_opt",
                "etg_sac_store_opt", "etg_sac_learn", "etg_sac_learn_replay", "etg_sac_grads", "etg_sac_sync_policy"]
+# ... and include/etgsim_bc.h
+BC_SYMBOLS = ["etg_bc_create", "etg_bc_destroy", "etg_bc_set_hyper", "etg_bc_load", "etg_bc_store", "etg_bc_load_opt",
+              "etg_bc_store_opt", "etg_bc_set_teacher", "etg_bc_learn", "etg_bc_learn_replay", "etg_bc_grads", "etg_bc_sync_policy"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 
@@ -106,6 +109,18 @@ def load():
     lib.etg_sac_learn_replay.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.etg_sac_grads.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(vp), vp]
     lib.etg_sac_sync_policy.argtypes = [vp, vp, vp]
+    lib.etg_bc_create.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+    lib.etg_bc_destroy.argtypes = [vp]
+    lib.etg_bc_set_hyper.argtypes = [vp, C.c_double, C.c_double]
+    lib.etg_bc_load.argtypes = [vp, C.POINTER(vp), i32, vp]
+    lib.etg_bc_store.argtypes = [vp, C.POINTER(vp), i32, vp]
+    lib.etg_bc_load_opt.argtypes = [vp, vp, vp, vp, vp]
+    lib.etg_bc_store_opt.argtypes = [vp, vp, vp, vp, vp]
+    lib.etg_bc_set_teacher.argtypes = [vp, C.POINTER(vp), vp]
+    lib.etg_bc_learn.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.etg_bc_learn_replay.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.etg_bc_grads.argtypes = [vp, vp, vp, i32, vp, vp, C.POINTER(vp), vp]
+    lib.etg_bc_sync_policy.argtypes = [vp, vp, vp]
     lib.etg_rollout_actions.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_prepare_next_dynamics.argtypes = [vp, vp, vp, vp]
     lib.etg_next_dynamics_pending.argtypes = [vp, vp, vp]

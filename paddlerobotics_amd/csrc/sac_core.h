@@ -162,13 +162,14 @@ __global__ void __launch_bounds__(256) k_gemm(int M, int N, int K, FA fa, FB fb,
 }
 
 // ------------------------------------------------------------------------------------------------------------- elementwise
+// The elementwise kernels are `static`: sac_learn.hip and bc_learn.hip both include this header, and each gets its own copy.
 // SAC.sample (alg/sac.py:65-76) from the head's pre-activations [n, 24] = {mean, log_std before the clamp}: 16 lanes per row.
 // A deliberate departure from the reference's fp32 arithmetic: Normal.log_prob evaluates -(x_t - mean)^2 / (2 std^2) with
 // x_t = mean + std * eps already rounded, so where std is tiny (log_std clamped at -20) x_t == mean in fp32 and its term is 0; here
 // the term is -eps^2 / 2, its exact value (what an fp64 run of the reference gives), as csrc/policy_mlp.hip's sample does.  It
 // enters logp' of the TD target and the reported actor loss; the gradients do not depend on it.
-__global__ void __launch_bounds__(256) k_sample(const float* __restrict__ head, const float* __restrict__ eps, int n,
-                                                float* __restrict__ act, float* __restrict__ logp) {
+static __global__ void __launch_bounds__(256) k_sample(const float* __restrict__ head, const float* __restrict__ eps, int n,
+                                                       float* __restrict__ act, float* __restrict__ logp) {
   const int row = blockIdx.x * 16 + (threadIdx.x >> 4), c = threadIdx.x & 15;
   const bool live = row < n && c < ACT;
   float lp = 0.0f;
@@ -193,10 +194,10 @@ __device__ inline void bump_step(long long* step, double* bc) {
 }
 
 // y = reward + gamma * terminal * (min(Q1t, Q2t) - alpha * logp');  dq[c] = 2 (q[c] - y) / n;  rows[c] = (q[c] - y)^2
-__global__ void __launch_bounds__(256) k_td(int n, int B, const float* __restrict__ rew, const float* __restrict__ term,
-                                            const long long* __restrict__ idx, const float* __restrict__ qt,
-                                            const float* __restrict__ logp, const float* __restrict__ q, float gamma, float alpha,
-                                            float* __restrict__ dq, float* __restrict__ rows, long long* step, double* bc) {
+static __global__ void __launch_bounds__(256) k_td(int n, int B, const float* __restrict__ rew, const float* __restrict__ term,
+                                                   const long long* __restrict__ idx, const float* __restrict__ qt,
+                                                   const float* __restrict__ logp, const float* __restrict__ q, float gamma, float alpha,
+                                                   float* __restrict__ dq, float* __restrict__ rows, long long* step, double* bc) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b == 0 && step) bump_step(step, bc);
   if (b >= n) return;
@@ -212,9 +213,9 @@ __global__ void __launch_bounds__(256) k_td(int n, int B, const float* __restric
 }
 
 // actor loss rows alpha * logp - min(Q1, Q2) and d loss / d q: -1 / n on the smaller critic of the row
-__global__ void __launch_bounds__(256) k_actor_dq(int n, int B, const float* __restrict__ q, const float* __restrict__ logp,
-                                                  float alpha, float* __restrict__ dq, float* __restrict__ rows, long long* step,
-                                                  double* bc) {
+static __global__ void __launch_bounds__(256) k_actor_dq(int n, int B, const float* __restrict__ q, const float* __restrict__ logp,
+                                                         float alpha, float* __restrict__ dq, float* __restrict__ rows, long long* step,
+                                                         double* bc) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b == 0 && step) bump_step(step, bc);
   if (b >= n) return;
@@ -228,8 +229,8 @@ __global__ void __launch_bounds__(256) k_actor_dq(int n, int B, const float* __r
 // backward of the sample: da = d loss / d action through the critics;  x = mean + exp(ls) eps, a = tanh(x),
 // logp_j = -eps^2 / 2 - ls - c - log(1 - a^2 + 1e-6):  d logp / d x = 2 a (1 - a^2) / (1 - a^2 + 1e-6),  d logp / d ls = -1 directly;
 // the clamp of log_std passes a gradient inside [-20, 2] only
-__global__ void __launch_bounds__(256) k_head_bwd(const float* __restrict__ head, const float* __restrict__ eps,
-                                                  const float* __restrict__ da, int n, float alpha, float* __restrict__ dhead) {
+static __global__ void __launch_bounds__(256) k_head_bwd(const float* __restrict__ head, const float* __restrict__ eps,
+                                                         const float* __restrict__ da, int n, float alpha, float* __restrict__ dhead) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n * ACT) return;
   const int row = i / ACT, c = i % ACT;
@@ -243,8 +244,8 @@ __global__ void __launch_bounds__(256) k_head_bwd(const float* __restrict__ head
 }
 
 // losses = {mean(rows_c[0]) + mean(rows_c[1]), mean(rows_a)}: one workgroup, a fixed summation order
-__global__ void __launch_bounds__(256) k_loss(int n, int B, const float* __restrict__ rows_c, const float* __restrict__ rows_a,
-                                              float* __restrict__ losses) {
+static __global__ void __launch_bounds__(256) k_loss(int n, int B, const float* __restrict__ rows_c, const float* __restrict__ rows_a,
+                                                     float* __restrict__ losses) {
   __shared__ float sm[3][256];
   const int t = threadIdx.x;
   float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
@@ -270,9 +271,9 @@ __device__ inline void adam1(float& p, float g, float& m, float& v, float nstep,
   p = __fadd_rn(p, __fmul_rn(nstep, __fdiv_rn(m, denom)));
 }
 
-__global__ void __launch_bounds__(256) k_adam(float* __restrict__ P, const float* __restrict__ G, float* __restrict__ M,
-                                              float* __restrict__ V, long n, double lr, const double* __restrict__ bc,
-                                              float* __restrict__ target, float tau, float decay) {
+static __global__ void __launch_bounds__(256) k_adam(float* __restrict__ P, const float* __restrict__ G, float* __restrict__ M,
+                                                     float* __restrict__ V, long n, double lr, const double* __restrict__ bc,
+                                                     float* __restrict__ target, float tau, float decay) {
   const float nstep = -(float)(lr / bc[0]), bc2s = (float)bc[1];
   const long n4 = n >> 2, stride = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {

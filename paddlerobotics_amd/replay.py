@@ -394,8 +394,9 @@ def collect_bc_pairs(env, rpm, max_step, student=None, action_bound=0.3, sensor_
     """The collection half of BCtrain.py:87-131, batched: every control step the student acts on ITS observation
     (cal_agent_obs: the 49-float row, optionally with obs2noise, without the 3 displacement columns) and the pair
     (student observation [46], teacher observation [49]) of every robot whose episode is still running is stored
-    (rpm = DeviceReplayMemory(max_size, 46, 49)); the learner later labels the pairs with the teacher's action
-    (BClearn).  mode: "sample" | "predict" (student policy) | "uniform" (the warm-up phase, BCtrain.py:101-102).
+    (rpm = DeviceReplayMemory(max_size, 46, 49)); the learner, bc.DeviceBC, later labels the pairs with the teacher's action
+    (DeviceBC.learn_epoch / learn_from on this memory = BClearn, BCtrain.py:128-138); `student` is that learner or its
+    `.policy`.  mode: "sample" | "predict" (student policy) | "uniform" (the warm-up phase, BCtrain.py:101-102).
     Returns (episode_return [N], episode_len [N])."""
     n, dev = env.num_envs, env.device
     adim = env.action_space.shape[0]
