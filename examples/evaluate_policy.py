@@ -41,11 +41,22 @@ def main():
     ap.add_argument("--act-bound", type=float, default=0.3)       # train.py:488
     ap.add_argument("--student", action="store_true", help="46-float observation (no BaseDisplacement), BCtrain.py:53-59")
     ap.add_argument("--frames", type=str, default="", help="write robot 0's frame of every step to this directory")
+    ap.add_argument("--sensor_dynamic", type=int, default=0, help="append the 48 dynamic parameters (train.py:270): 97 columns")
+    ap.add_argument("--RNN_mode", type=str, default="None", help="'stack': the actor reads --timesteps older observations too")
+    ap.add_argument("--timesteps", type=int, default=5)              # deployment/test.py:44-45
+    ap.add_argument("--timeinterval", type=int, default=1)
     args = ap.parse_args()
     if args.frames:
         os.makedirs(args.frames, exist_ok=True)
+    sensor_mode = {"dis": 0} if args.student else {}
+    if args.sensor_dynamic:
+        sensor_mode["dynamic_vec"] = 1
+    if args.RNN_mode != "None":
+        if args.RNN_mode != "stack":
+            raise SystemExit("--RNN_mode must be 'stack' (the actor is an MLP over the flattened history) or 'None'")
+        sensor_mode["RNN"] = {"time_steps": args.timesteps, "time_interval": args.timeinterval, "mode": "stack"}
     env = make_env("Quadrupedal", num_envs=args.num_envs, device="cuda:0", task=args.task, ETG_path=args.etg,
-                   sensor_mode={"dis": 0} if args.student else None)
+                   sensor_mode=sensor_mode or None)
     obs_dim = env.observation_space.shape[0]
     pol = MfmaPolicy(obs_dim, 12)
     if args.actor:

@@ -392,7 +392,10 @@ int etg_set_contact_impulses(EtgHandle* h, const float* lam, void* stream);
 /* ---- policy (the one dense contraction, model/mujoco_model.py:44-60) -----
  * act = tanh(W3 relu(W2 relu(W1 obs + b1) + b2) + b3) * act_scale
  * weights are torch [out,in] row-major fp32 device pointers; obs [N,in_dim],
- * act [N,12].  precision: 0 = fp32 MFMA (exact f32), 1 = bf16 MFMA.           */
+ * act [N,12].  precision: 0 = fp32 MFMA (exact f32), 1 = bf16 MFMA.
+ * etg_policy_create takes in_dim 1..512 (hidden 256, out_dim 1..16; anything else: ETG_ERR_BAD_ARG).  A policy of in_dim > 64
+ * serves etg_policy_forward / etg_policy_sample only: the entry points that run the actor inside another kernel (the
+ * closed-loop rollouts, the one-launch control step) and the learners' policy-sync calls return ETG_ERR_BAD_ARG for it. */
 typedef struct EtgPolicy EtgPolicy;
 int etg_policy_create(int in_dim, int hidden, int out_dim, int device, EtgPolicy** out);
 int etg_policy_load(EtgPolicy* p, const float* w1, const float* b1, const float* w2,

@@ -318,6 +318,7 @@ extern "C" int etg_bc_grads(EtgBc* h, const float* obs, const float* ref_obs, in
 extern "C" int etg_bc_sync_policy(EtgBc* h, EtgPolicy* p, void* stream) {
   if (!h) return bfail(ETG_ERR_BAD_ARG, "etg_bc_sync_policy: null handle");
   if (!p) return bfail(ETG_ERR_BAD_ARG, "etg_bc_sync_policy: null policy");
+  if (p->in_dim > 64) return bfail(ETG_ERR_BAD_ARG, "etg_bc_sync_policy: the learner and its policy sync take observations of in_dim <= 64");
   if (p->in_dim != h->ds || p->hidden != HID || p->out_dim != ACT || p->device != h->device)
     return bfail(ETG_ERR_BAD_ARG, "etg_bc_sync_policy: the policy's dimensions or device differ from the learner's");
   const float* P = h->P;

@@ -2769,6 +2769,10 @@ extern "C" int etg_rollout_actions(EtgHandle* h, const float* actions, int n_ste
 // ---- the closed-loop entry points (etg_rollout_policy, etg_rollout_policy_record, etg_step_policy): what they ask of the
 // policy, and the two forms its weights are handed to the kernels in.  fn: the entry point's name for the error text
 static int policy_checks(const char* fn, const EtgHandle* h, const EtgPolicy* pol, int obs_col0) {
+  // (a wider policy -- etg_policy_create takes up to 512 columns -- has neither the 4 k-blocks of w1 nor the per-wave stream)
+  if (pol->in_dim > 4 * pol::KQ1)
+    return fail(ETG_ERR_BAD_ARG, std::string(fn) + ": the fused closed-loop kernels take a policy of in_dim <= 64 (wider ones: "
+                                                   "etg_policy_forward / etg_policy_sample, then etg_step)");
   if (pol->device != h->device) return fail(ETG_ERR_BAD_ARG, std::string(fn) + ": policy and simulator live on different devices");
   if (obs_col0 < 0 || obs_col0 + pol->in_dim > ETG_OBS_DIM || pol->out_dim != ETG_ACT_DIM)
     return fail(ETG_ERR_BAD_ARG, std::string(fn) + ": the policy must map observation columns [col0, col0 + in_dim) to 12 actions");

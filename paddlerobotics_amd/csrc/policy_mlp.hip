@@ -146,11 +146,171 @@ __global__ void __launch_bounds__(THREADS) k_policy(const float* __restrict__ ob
   }
 }
 
+// ---- observations of 65 .. MAX_IN columns (privileged-dynamics rows, stacked history): k_policy_wide ----
+// The same tile as k_policy -- 16 robots per workgroup, NW waves, activations in LDS -- with the observation tile in an LDS
+// buffer of its own (16 x Kpad, Kpad = in_dim rounded up to 32 so that the bf16 path's k-block pairs stay whole) and layer 1's K
+// in a runtime loop over Kpad / 32 pairs of k-blocks.  w1p holds Kpad / 16 k-blocks per tile (etg_policy_create / _load).
+constexpr int MAX_IN = 512;
+constexpr int XS = MAX_IN + 4;   // row stride of the observation tile (as HS: rotates the 16-byte slots by one per row)
+
+// out[16][this wave's 16 * TPW columns] = relu(x[16][32 nkp] W1^T + b1).  The accumulators stay in registers over the whole loop;
+// the weight fragments of R - 1 pairs are in flight in a register ring of R slots (pair kp lives in slot kp % R; the loop runs in
+// groups of R pairs so that the slots are static, and the last nkp % R pairs follow it: their fragments are in the ring by then).
+// Summation order of precision 0, per output: ONE fmaf chain (v_mfma_f32_16x16x4_f32 is bitwise an fmaf chain) that starts at
+// 0, takes the 16-column k-blocks in ascending order and, inside a k-block, the columns k = 16 kb + 4 g + c with c = 0..3 outer
+// and the instruction's four k-slots g = 0..3 inner (the order hidden_layer has); the bias is added after the last block.
+template <bool BF16>
+__device__ __forceinline__ void wide_layer1(const float* x, const float4* __restrict__ wp, const float* __restrict__ b, float* out,
+                                            int nkp, int wave, int lane) {
+  constexpr int TPW = (HID / 16) / NW;
+  constexpr int R = TPW <= 2 ? 4 : 2;
+  constexpr int F = BF16 ? 1 : 2;   // 16-byte fragments per pair and tile: one bf16x8, or the fp32 ones of its two k-blocks
+  const int i = lane & 15, g = lane >> 4;
+  f32x4 acc[TPW];
+#pragma unroll
+  for (int t = 0; t < TPW; t++) acc[t] = {0.f, 0.f, 0.f, 0.f};
+  const float* xr = x + i * XS + 4 * g;
+  const int tstride = nkp * F * 64;
+  const float4* base = wp + (size_t)(TPW * wave) * tstride + lane;
+  float4 w[R][F][TPW];
+  auto fetch = [&](int slot, int kp) {
+    const int kq = kp < nkp ? kp : nkp - 1;   // (past the end: the last pair again, unused)
+#pragma unroll
+    for (int f = 0; f < F; f++)
+#pragma unroll
+      for (int t = 0; t < TPW; t++) w[slot][f][t] = base[t * tstride + (kq * F + f) * 64];
+  };
+  auto mac = [&](int slot, int kp) {
+    const float4 a0 = *reinterpret_cast<const float4*>(xr + 32 * kp);
+    const float4 a1 = *reinterpret_cast<const float4*>(xr + 32 * kp + 16);
+    if constexpr (!BF16) {
+#pragma unroll
+      for (int f = 0; f < F; f++) {
+        const float4 a = f ? a1 : a0;
+#pragma unroll
+        for (int t = 0; t < TPW; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[slot][f][t].x, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < TPW; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[slot][f][t].y, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < TPW; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[slot][f][t].z, acc[t], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < TPW; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[slot][f][t].w, acc[t], 0, 0, 0);
+      }
+    } else {
+      const bf16x8 av = pack_bf16(a0, a1);
+#pragma unroll
+      for (int t = 0; t < TPW; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, as_bf16x8(w[slot][0][t]), acc[t], 0, 0, 0);
+    }
+  };
+#pragma unroll
+  for (int p = 0; p < R - 1; p++) fetch(p, p);
+  int kp0 = 0;
+#pragma unroll 1
+  for (; kp0 + R <= nkp; kp0 += R) {
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+      fetch((j + R - 1) % R, kp0 + j + R - 1);   // into the slot the step before this one read
+      __builtin_amdgcn_sched_barrier(0);         // keep the fetches R - 1 pairs ahead (see hidden_layer)
+      mac(j, kp0 + j);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < R - 1; j++)
+    if (kp0 + j < nkp) mac(j, kp0 + j);   // (wave-uniform)
+#pragma unroll
+  for (int t = 0; t < TPW; t++) {
+    const int col = 16 * TPW * wave + 16 * t + i;
+    const float bias = b[col];
+#pragma unroll
+    for (int r = 0; r < 4; r++) out[(4 * g + r) * HS + col] = fmaxf(acc[t][r] + bias, 0.0f);
+  }
+}
+
+// Layers 2 and 3 and the head's epilogue of a 16-robot tile whose layer-1 activations are in bufB: the part of the forward that
+// does not depend on the observation's width, as k_policy has it (same calls, same order of every sum).  k_policy keeps its
+// own text so that the code generated for the <= 64-column path does not move.
+template <bool BF16, bool SAMPLE>
+__device__ __forceinline__ void policy_tail(float* bufA, float* bufB, float (*part)[NW][TM][16], int tid, int wave, int lane, int n, int row0,
+                                            const float4* __restrict__ w2p, const float* __restrict__ b2,
+                                            const float4* __restrict__ w3p, const float* __restrict__ b3,
+                                            const float4* __restrict__ w3sp, const float* __restrict__ b3s,
+                                            const float* __restrict__ eps, int out_dim, float scale,
+                                            float* __restrict__ act, float* __restrict__ logp) {
+  hidden_layer<BF16, HID / 16, NW>(bufB, w2p, b2, bufA, wave, lane);
+  __syncthreads();
+  // output layer: one 16x16 tile per head (out_dim <= 16), K split over the waves
+  output_partial<BF16, NW>(bufA, w3p, wave, lane, part[0]);
+  if constexpr (SAMPLE) output_partial<BF16, NW>(bufA, w3sp, wave, lane, part[1]);
+  __syncthreads();
+  {
+    const int r = tid >> 4, cidx = tid & 15;  // first 256 threads = 16 rows x 16 cols; a row = one 16-lane DPP row
+    if (r >= TM) return;
+    const bool live = cidx < out_dim && row0 + r < n;
+    // fixed summation order over the NW K-slices
+    float v = 0.0f;
+#pragma unroll
+    for (int q = 0; q < NW; q += 2) v += part[0][q][r][cidx] + part[0][q + 1][r][cidx];
+    v += live ? b3[cidx] : 0.0f;
+    float lp = 0.0f;
+    if constexpr (SAMPLE) {
+      float ls = 0.0f;
+#pragma unroll
+      for (int q = 0; q < NW; q += 2) ls += part[1][q][r][cidx] + part[1][q + 1][r][cidx];
+      ls += live ? b3s[cidx] : 0.0f;
+      ls = fminf(fmaxf(ls, -20.0f), 2.0f);
+      const float e = live ? eps[(size_t)(row0 + r) * out_dim + cidx] : 0.0f;
+      v = v + expf(ls) * e;
+      const float a = tanhf(v);
+      lp = live ? (-0.5f * e * e - ls - 0.9189385332046727f) - logf((1.0f - a * a) + 1e-6f) : 0.0f;
+      if (live) act[(size_t)(row0 + r) * out_dim + cidx] = a * scale;
+      if (logp) {   // sum over the row's 16 lanes (butterfly inside the DPP row)
+        lp += __shfl_xor(lp, 1); lp += __shfl_xor(lp, 2); lp += __shfl_xor(lp, 4); lp += __shfl_xor(lp, 8);
+        if (cidx == 0 && row0 + r < n) logp[row0 + r] = lp;
+      }
+    } else {
+      if (live) act[(size_t)(row0 + r) * out_dim + cidx] = tanhf(v) * scale;
+    }
+  }
+}
+
+template <bool BF16, bool SAMPLE>
+__global__ void __launch_bounds__(THREADS) k_policy_wide(const float* __restrict__ obs, int n, int in_dim,
+                                                         const float4* __restrict__ w1p, const float* __restrict__ b1,
+                                                         const float4* __restrict__ w2p, const float* __restrict__ b2,
+                                                         const float4* __restrict__ w3p, const float* __restrict__ b3,
+                                                         const float4* __restrict__ w3sp, const float* __restrict__ b3s,
+                                                         const float* __restrict__ eps, int out_dim, float scale,
+                                                         float* __restrict__ act, float* __restrict__ logp) {
+  __shared__ __attribute__((aligned(16))) float xbuf[TM * XS];
+  __shared__ __attribute__((aligned(16))) float bufA[TM * HS];
+  __shared__ __attribute__((aligned(16))) float bufB[TM * HS];
+  __shared__ float part[SAMPLE ? 2 : 1][NW][TM][16];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int row0 = blockIdx.x * TM;
+  const int kpad = (in_dim + 31) & ~31;   // <= MAX_IN (etg_policy_create)
+  // obs tile -> LDS: a wave per row, its lanes along the row.  Rows lie in_dim floats apart, so for most widths they are not
+  // 16-byte aligned: 4-byte loads, coalesced.  Rows past n and columns in_dim .. kpad - 1 are written as zeros (the weights
+  // are zero there, but 0 x whatever the LDS held is not 0)
+  for (int r = wave; r < TM; r += NW) {
+    const bool live = row0 + r < n;
+    const float* src = obs + (size_t)(row0 + r) * in_dim;
+    for (int c = lane; c < kpad; c += 64) xbuf[r * XS + c] = (live && c < in_dim) ? src[c] : 0.0f;
+  }
+  __syncthreads();
+  wide_layer1<BF16>(xbuf, w1p, b1, bufB, kpad / 32, wave, lane);
+  __syncthreads();
+  policy_tail<BF16, SAMPLE>(bufA, bufB, part, tid, wave, lane, n, row0, w2p, b2, w3p, b3, w3sp, b3s, eps, out_dim, scale, act, logp);
+}
+
 }  // namespace
 
 extern "C" void etg_set_last_error_(const char* msg);
 
 static size_t packed_floats(int ntiles, int nkb) { return (size_t)ntiles * nkb * 64 * 4; }
+
+// k-blocks of layer 1 in w1 / w1h: the 64 padded columns of k_policy (and of the closed-loop kernels that read w1), or k_policy_wide's
+// Kpad / 16
+static int l1_kblocks(int in_dim) { return in_dim <= 64 ? 4 : 2 * ((in_dim + 31) / 32); }
 
 static int pfail(int code, const char* msg) {
   etg_set_last_error_(msg);
@@ -158,19 +318,20 @@ static int pfail(int code, const char* msg) {
 }
 
 extern "C" int etg_policy_create(int in_dim, int hidden, int out_dim, int device, EtgPolicy** out) {
-  if (!out || in_dim <= 0 || in_dim > 64 || hidden != HID || out_dim <= 0 || out_dim > 16)
-    return pfail(ETG_ERR_BAD_ARG, "etg_policy_create: need in_dim<=64, hidden==256, out_dim<=16");
+  if (!out || in_dim <= 0 || in_dim > MAX_IN || hidden != HID || out_dim <= 0 || out_dim > 16)
+    return pfail(ETG_ERR_BAD_ARG, "etg_policy_create: need in_dim<=512, hidden==256, out_dim<=16");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return pfail(ETG_ERR_NO_DEVICE, "etg_policy_create: no HIP device");
   if (device < 0 || device >= ndev) return pfail(ETG_ERR_BAD_ARG, "etg_policy_create: bad device");
   if (hipSetDevice(device) != hipSuccess) return pfail(ETG_ERR_HIP, "hipSetDevice");
   EtgPolicy* p = new EtgPolicy();
   p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->out_dim = out_dim;
-  struct { float** q; size_t n; } a[] = {{&p->w1, packed_floats(HID / 16, 4)}, {&p->b1, (size_t)hidden},
+  const int nkb1 = l1_kblocks(in_dim);
+  struct { float** q; size_t n; } a[] = {{&p->w1, packed_floats(HID / 16, nkb1)}, {&p->b1, (size_t)hidden},
                                          {&p->w2, packed_floats(HID / 16, HID / 16)}, {&p->b2, (size_t)hidden},
                                          {&p->w3, packed_floats(1, HID / 16)}, {&p->b3, (size_t)out_dim},
                                          {&p->w3s, packed_floats(1, HID / 16)}, {&p->b3s, (size_t)out_dim},
-                                         {&p->w1h, packed_floats(HID / 16, 4) / 2}, {&p->w2h, packed_floats(HID / 16, HID / 16) / 2},
+                                         {&p->w1h, packed_floats(HID / 16, nkb1) / 2}, {&p->w2h, packed_floats(HID / 16, HID / 16) / 2},
                                          {&p->w3h, packed_floats(1, HID / 16) / 2}, {&p->w3sh, packed_floats(1, HID / 16) / 2},
                                          {&p->w12q, (size_t)KG * NCHW * 256}, {&p->w3q, (size_t)KQH * 256}, {&p->w3sq, (size_t)KQH * 256}};
   p->has_std = 0;
@@ -186,7 +347,7 @@ extern "C" int etg_policy_load(EtgPolicy* p, const float* w1, const float* b1, c
   if (hipSetDevice(p->device) != hipSuccess) return pfail(ETG_ERR_HIP, "hipSetDevice");
   hipStream_t s = (hipStream_t)stream;
   struct { float* d; const float* src; int nout, kdim, ntiles, nkb; float* dh; } pk[] = {
-      {p->w1, w1, p->hidden, p->in_dim, HID / 16, 4, p->w1h},
+      {p->w1, w1, p->hidden, p->in_dim, HID / 16, l1_kblocks(p->in_dim), p->w1h},
       {p->w2, w2, p->hidden, p->hidden, HID / 16, HID / 16, p->w2h},
       {p->w3, w3, p->out_dim, p->hidden, 1, HID / 16, p->w3h}};
   for (auto& x : pk) {
@@ -232,12 +393,13 @@ extern "C" int etg_policy_forward(EtgPolicy* p, const float* obs, int n, float a
   if (!p || !obs || !act || n <= 0) return pfail(ETG_ERR_BAD_ARG, "etg_policy_forward: bad arguments");
   if (hipSetDevice(p->device) != hipSuccess) return pfail(ETG_ERR_HIP, "hipSetDevice");
   dim3 grid((n + TM - 1) / TM), block(THREADS);
+  const bool wide = p->in_dim > 64;   // (<= 64: k_policy, launched exactly as before k_policy_wide existed)
+  const auto k32 = wide ? k_policy_wide<false, false> : k_policy<false, false>;
+  const auto k16 = wide ? k_policy_wide<true, false> : k_policy<true, false>;
   if (precision == 0)
-    hipLaunchKernelGGL((k_policy<false, false>), grid, block, 0, (hipStream_t)stream, ETG_POLICY_ARGS, nullptr, p->out_dim,
-                       act_scale, act, nullptr);
+    hipLaunchKernelGGL(k32, grid, block, 0, (hipStream_t)stream, ETG_POLICY_ARGS, nullptr, p->out_dim, act_scale, act, nullptr);
   else
-    hipLaunchKernelGGL((k_policy<true, false>), grid, block, 0, (hipStream_t)stream, ETG_POLICY_ARGS_BF16, nullptr, p->out_dim,
-                       act_scale, act, nullptr);
+    hipLaunchKernelGGL(k16, grid, block, 0, (hipStream_t)stream, ETG_POLICY_ARGS_BF16, nullptr, p->out_dim, act_scale, act, nullptr);
   if (hipGetLastError() != hipSuccess) return pfail(ETG_ERR_HIP, "etg_policy_forward: launch failed");
   return ETG_OK;
 }
@@ -248,12 +410,13 @@ extern "C" int etg_policy_sample(EtgPolicy* p, const float* obs, int n, const fl
   if (!p->has_std) return pfail(ETG_ERR_STATE, "etg_policy_sample: etg_policy_load_std() first");
   if (hipSetDevice(p->device) != hipSuccess) return pfail(ETG_ERR_HIP, "hipSetDevice");
   dim3 grid((n + TM - 1) / TM), block(THREADS);
+  const bool wide = p->in_dim > 64;   // (<= 64: k_policy, launched exactly as before k_policy_wide existed)
+  const auto k32 = wide ? k_policy_wide<false, true> : k_policy<false, true>;
+  const auto k16 = wide ? k_policy_wide<true, true> : k_policy<true, true>;
   if (precision == 0)
-    hipLaunchKernelGGL((k_policy<false, true>), grid, block, 0, (hipStream_t)stream, ETG_POLICY_ARGS, noise, p->out_dim,
-                       act_scale, act, logp);
+    hipLaunchKernelGGL(k32, grid, block, 0, (hipStream_t)stream, ETG_POLICY_ARGS, noise, p->out_dim, act_scale, act, logp);
   else
-    hipLaunchKernelGGL((k_policy<true, true>), grid, block, 0, (hipStream_t)stream, ETG_POLICY_ARGS_BF16, noise, p->out_dim,
-                       act_scale, act, logp);
+    hipLaunchKernelGGL(k16, grid, block, 0, (hipStream_t)stream, ETG_POLICY_ARGS_BF16, noise, p->out_dim, act_scale, act, logp);
   if (hipGetLastError() != hipSuccess) return pfail(ETG_ERR_HIP, "etg_policy_sample: launch failed");
   return ETG_OK;
 }

@@ -300,6 +300,7 @@ extern "C" int etg_sac_grads(EtgSac* h, const float* obs, const float* act, cons
 extern "C" int etg_sac_sync_policy(EtgSac* h, EtgPolicy* p, void* stream) {
   if (!h) return sfail(ETG_ERR_BAD_ARG, "etg_sac_sync_policy: null handle");
   if (!p) return sfail(ETG_ERR_BAD_ARG, "etg_sac_sync_policy: null policy");
+  if (p->in_dim > 64) return sfail(ETG_ERR_BAD_ARG, "etg_sac_sync_policy: the learner and its policy sync take observations of in_dim <= 64");
   if (p->in_dim != h->d || p->hidden != HID || p->out_dim != ACT || p->device != h->device)
     return sfail(ETG_ERR_BAD_ARG, "etg_sac_sync_policy: the policy's dimensions or device differ from the learner's");
   const float* P = h->P;

@@ -17,8 +17,13 @@ def _ptr(t):
 
 
 class MfmaPolicy:
+    MAX_OBS_DIM = 512        # predict() / sample(): csrc/policy_mlp.hip, k_policy up to 64 columns, k_policy_wide above
+    MAX_FUSED_OBS_DIM = 64   # env.rollout_policy / rollout_policy_record / step_policy and the learners' policy sync
+
     def __init__(self, obs_dim, action_dim=12, hidden=256, device="cuda:0"):
         self.obs_dim, self.action_dim, self.hidden = int(obs_dim), int(action_dim), int(hidden)
+        if not 1 <= self.obs_dim <= self.MAX_OBS_DIM:
+            raise ValueError("obs_dim must be in 1..%d" % self.MAX_OBS_DIM)
         self.device = torch.device(device)
         self._lib = _lib.load()
         self._h = C.c_void_p()
