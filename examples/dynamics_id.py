@@ -6,7 +6,9 @@ workers x K candidates, here every candidate is one robot of the batch).
 
 There are no robot recordings in the reference tree (`mean_dict` comes from the SharePoint data folder), so this example
 manufactures them: a robot with hidden "true" parameters replays two gaits, and the ES is asked to recover a parameter
-vector that reproduces those recordings.  Usage: python examples/dynamics_id.py [--popsize 1024] [--generations 20]"""
+vector that reproduces those recordings.  Usage: python examples/dynamics_id.py [--popsize 1024] [--generations 20]
+[--alg ga|ses|pepg|openes|simples] (the solvers of Dynamic_train.py --alg; cma is not provided, it needs the `cma` package)
+[--log FILE] appends one line per generation with the best fitness and the device time of ask() + tell()."""
 import argparse
 import os
 import sys
@@ -18,9 +20,19 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from paddlerobotics_amd import a1_model as A  # noqa: E402
 from paddlerobotics_amd.env import make_env  # noqa: E402
-from paddlerobotics_amd.es import SimpleGA  # noqa: E402
+from paddlerobotics_amd.es import ALGS, make_solver  # noqa: E402
 from paddlerobotics_amd.etg import ETG_layer, Opt_with_points, etg_joint_action  # noqa: E402
 from paddlerobotics_amd import rollout as R  # noqa: E402
+
+
+def timed(fn, start, stop):
+    """fn with a device event recorded before and after it"""
+    def call(*args):
+        start.record()
+        out = fn(*args)
+        stop.record()
+        return out
+    return call
 
 
 def main():
@@ -30,6 +42,8 @@ def main():
     ap.add_argument("--steps", type=int, default=100)          # e_step of sample_episode, Dynamic_parallel_model.py:53
     ap.add_argument("--sigma", type=float, default=0.1)
     ap.add_argument("--device", type=str, default="cuda:0")
+    ap.add_argument("--alg", type=str, default="ga", help="one of " + ", ".join(ALGS))
+    ap.add_argument("--log", type=str, default=None, help="append best fitness and ask + tell device time per generation to this file")
     ap.add_argument("--step-loop", action="store_true",
                     help="replay through env.step() per control step (the reference's loop shape) instead of the fused action-tape rollout")
     args = ap.parse_args()
@@ -56,17 +70,26 @@ def main():
         mean_dict[key + "_motor_mean"], mean_dict[key + "_drpy_mean"] = np.array(mot), np.array(dr)
         mean_dict[key + "_motor_std"], mean_dict[key + "_drpy_std"] = np.full((T, 12), 0.05), np.full((T, 3), 0.5)
     evaluate = R.make_dynamics_id_evaluator(env, gait, mean_dict, e_steps=T, fused=not args.step_loop)
-    solver = SimpleGA(48, sigma_init=args.sigma, sigma_decay=0.995, sigma_limit=0.02, elite_ratio=0.1, weight_decay=0.005,
-                      popsize=N, param=np.zeros(48), device=args.device)                     # ES_ParallelModel defaults
+    solver = make_solver(args.alg, 48, N, args.sigma, 0.995, param=np.zeros(48), device=args.device)   # ES_ParallelModel.set_solver
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)]                     # around ask() and around tell()
+    solver.ask, solver.tell = timed(solver.ask, marks[0], marks[1]), timed(solver.tell, marks[2], marks[3])
     for g in range(args.generations):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         fit = R.es_generation(solver, evaluate)
         torch.cuda.synchronize()
-        best = solver.get_best_param().cpu().numpy()
-        print("gen %2d  reward max %7.3f mean %7.3f | |best - truth| on kp/kd/mass %.3f | %.2f s (%.1f M env-steps/s)" % (
-            g, fit.max().item(), fit.mean().item(), np.abs(best - truth)[[2, 6, 7, 8] + list(range(21, 45))].mean(),
-            time.perf_counter() - t0, N * 2 * T / (time.perf_counter() - t0) / 1e6))
+        dt = time.perf_counter() - t0
+        result = solver.result()
+        best = result[0].cpu().numpy()
+        sig = float(torch.as_tensor(result[3]).mean())                                   # update(): sig = np.mean(result[3])
+        ask_tell_ms = marks[0].elapsed_time(marks[1]) + marks[2].elapsed_time(marks[3])
+        print("gen %2d  reward max %7.3f mean %7.3f sigma %.4f | |best - truth| on kp/kd/mass %.3f | %.2f s (%.1f M env-steps/s) | "
+              "ask + tell %.3f ms" % (g, fit.max().item(), fit.mean().item(), sig,
+                                      np.abs(best - truth)[[2, 6, 7, 8] + list(range(21, 45))].mean(), dt, N * 2 * T / dt / 1e6, ask_tell_ms))
+        if args.log:
+            with open(args.log, "a") as f:
+                f.write("alg %-7s popsize %d gen %2d  best fitness %.4f  generation max %.4f  sigma %.4f  ask+tell %.3f ms  generation %.1f ms\n"
+                        % (args.alg, N, g, result[1], fit.max().item(), sig, ask_tell_ms, dt * 1e3))
     np.save("dynamic_param_identified.npy", solver.get_best_param().cpu().numpy())            # ES_ParallelModel.save
 
 

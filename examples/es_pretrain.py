@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from paddlerobotics_amd.env import make_env  # noqa: E402
-from paddlerobotics_amd.es import SimpleGA  # noqa: E402
+from paddlerobotics_amd.es import ALGS, SimpleGA, make_solver  # noqa: E402
 from paddlerobotics_amd.etg import ETG_layer, Opt_with_points  # noqa: E402
 from paddlerobotics_amd import rollout as R  # noqa: E402
 
@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--generations", type=int, default=10)
     ap.add_argument("--max-step", type=int, default=400)
     ap.add_argument("--sigma", type=float, default=0.02)
+    ap.add_argument("--alg", type=str, default="ga", help="one of " + ", ".join(ALGS) + " (other than ga: with the settings of Dynamic_train.py --alg)")
     args = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", 1), ("RANK", 0), ("LOCAL_RANK", 0)))
     dist = None
@@ -40,6 +41,8 @@ def main():
     w0, b0, prior = Opt_with_points(layer, ETG_T=0.5, Footheight=0.1, Steplength=0.05)     # train.py:298-299
     solver = SimpleGA(12, sigma_init=args.sigma, sigma_decay=0.99, sigma_limit=0.005, elite_ratio=0.1,
                       weight_decay=0.005, popsize=args.popsize, param=np.zeros(12), device=dev)  # train.py:288-295
+    if args.alg != "ga":
+        solver = make_solver(args.alg, 12, args.popsize, args.sigma, 0.99, param=np.zeros(12), device=dev)
     evaluate = R.make_etg_evaluator(env, layer, 0.5, prior, w0, b0, max_step=args.max_step)
     for g in range(args.generations):
         torch.cuda.synchronize()
