@@ -13,7 +13,7 @@ import torch
 
 from paddlerobotics_amd.bc import DeviceBC
 from paddlerobotics_amd.replay import DeviceReplayMemory, collect_bc_pairs
-from paddlerobotics_amd.sac import DeviceSAC, KEYS, actor_forward, init_like_reference
+from paddlerobotics_amd.sac import DeviceSAC, KEYS, CRITIC_KEYS, actor_forward, init_like_reference
 
 from tests import bc_fixture as FX
 from tests import sac_fixture as SX
@@ -351,3 +351,59 @@ def test_it_learns_to_imitate_the_teacher():
           % (b0, e_fused, e32, e64, dev, own, bound))
     assert e_fused < b0, (b0, e_fused)
     assert dev <= bound, (dev, bound)
+
+
+# ------------------------------------------------------------- 10: checkpoints and hyper-parameters on the fused path
+ROWS = 37             # not a multiple of the 32-row tile: edge tiles in every contraction
+
+
+def _step(agent, u):
+    """update u of the fixture on its first ROWS rows"""
+    return agent.learn(*[t[:ROWS] for t in _dev(FX.pairs(u))], noise=[t[:ROWS] for t in _dev(FX.noise(u))])
+
+
+def _changed(before, after, keys):
+    return [not torch.equal(before[k], after[k]) for k in keys]
+
+
+@pytest.mark.gpu
+def test_fused_resume_continues_with_the_same_bits():
+    _need_gpu()
+    a = _fixture_agent(max_batch=64)
+    for u in (1, 2, 3):
+        _step(a, u)
+    b = DeviceBC(FX.STUDENT_DIM, FX.TEACHER_DIM, max_batch=64, device=DEV, seed=7, **FX.HYPER)
+    b.load_state_dict(a.state_dict())
+    b.load_optimizer_state(a.optimizer_state())
+    b.set_teacher(_teacher_sd())
+    _step(a, 4), _step(b, 4)
+    oa, ob = a.optimizer_state(), b.optimizer_state()
+    assert _same(a, b)
+    assert sorted(oa) == sorted(ob) == ["exp_avg", "exp_avg_sq", "steps"]
+    assert all(torch.equal(oa[f][k], ob[f][k]) for f in ("exp_avg", "exp_avg_sq") for k in oa[f])
+    assert list(oa["exp_avg"]) == list(oa["exp_avg_sq"]) == KEYS
+    assert oa["steps"] == ob["steps"] == [4, 4]
+    c = DeviceBC(FX.STUDENT_DIM, FX.TEACHER_DIM, max_batch=64, device=DEV, seed=8, **FX.HYPER)
+    c.load_state_dict(a.state_dict())                      # without the optimizer's state: the optimizers start afresh
+    c.set_teacher(_teacher_sd())
+    _step(c, 5)
+    assert c.optimizer_state()["steps"] == [1, 1]
+
+
+@pytest.mark.gpu
+def test_fused_set_hyper_reaches_the_next_update():
+    _need_gpu()
+    actor, critic = KEYS[:8], CRITIC_KEYS
+    a = _fixture_agent(max_batch=64)
+    before = a.state_dict()
+    a.set_hyper(actor_lr=0.0)
+    _step(a, 1)
+    after = a.state_dict()
+    assert not any(_changed(before, after, actor)) and all(_changed(before, after, critic[::2]))
+    a.set_hyper(actor_lr=FX.HYPER["actor_lr"], critic_lr=0.0)
+    before = after
+    _step(a, 2)
+    after = a.state_dict()
+    assert not any(_changed(before, after, critic)) and all(_changed(before, after, actor[::2]))
+    with pytest.raises(TypeError):
+        a.set_hyper(tau=0.5)

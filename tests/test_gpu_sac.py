@@ -27,8 +27,8 @@ def gold():
     return np.load(os.path.join(ROOT, "tests", "golden", "sac_learn.npz"))
 
 
-def _fixture_agent(fused=True):
-    agent = DeviceSAC(FX.OBS_DIM, FX.ACT_DIM, max_batch=FX.BATCH, device=DEV, fused=fused, **FX.HYPER)
+def _fixture_agent(fused=True, max_batch=FX.BATCH):
+    agent = DeviceSAC(FX.OBS_DIM, FX.ACT_DIM, max_batch=max_batch, device=DEV, fused=fused, **FX.HYPER)
     agent.load_state_dict({k: torch.as_tensor(v) for k, v in FX.init_params().items()})
     return agent
 
@@ -321,3 +321,76 @@ def test_it_learns_a_contextual_bandit():
     spread = max(others) - min(others)
     print("[sac] bandit, definition: same seed %.4f, other seeds %s, spread %.4f" % (yard, ["%.4f" % x for x in others], spread))
     assert abs(r1 - yard) <= spread, (r1, yard, spread)
+
+
+# ------------------------------------------------- 9: checkpoints, hyper-parameters and the explicit target sync on the fused path
+ROWS = 37             # not a multiple of the 32-row tile: edge tiles in every contraction
+
+
+def _step(agent, u):
+    """update u of the fixture on its first ROWS rows"""
+    return agent.learn(*[t[:ROWS] for t in _dev(FX.batch(u))], noise=[t[:ROWS] for t in _dev(FX.noise(u))])
+
+
+def _changed(before, after, keys):
+    return [not torch.equal(before[k], after[k]) for k in keys]
+
+
+@pytest.mark.gpu
+def test_fused_resume_continues_with_the_same_bits():
+    _need_gpu()
+    a = _fixture_agent(max_batch=64)
+    for u in (1, 2, 3):
+        _step(a, u)
+    b = DeviceSAC(FX.OBS_DIM, FX.ACT_DIM, max_batch=64, device=DEV, seed=7, **FX.HYPER)
+    b.load_state_dict(a.state_dict())
+    b.load_optimizer_state(a.optimizer_state())
+    _step(a, 4), _step(b, 4)
+    sa, sb, oa, ob = a.state_dict(), b.state_dict(), a.optimizer_state(), b.optimizer_state()
+    assert all(torch.equal(sa[k], sb[k]) for k in KEYS)
+    assert sorted(oa) == sorted(ob) == ["exp_avg", "exp_avg_sq", "steps", "target"]
+    assert all(torch.equal(oa[f][k], ob[f][k]) for f in ("target", "exp_avg", "exp_avg_sq") for k in oa[f])
+    assert list(oa["target"]) == CRITIC_KEYS and list(oa["exp_avg"]) == list(oa["exp_avg_sq"]) == KEYS
+    assert oa["steps"] == ob["steps"] == [4, 4]
+    c = DeviceSAC(FX.OBS_DIM, FX.ACT_DIM, max_batch=64, device=DEV, seed=8, **FX.HYPER)
+    c.load_state_dict(a.state_dict())                      # without the optimizer's state: the optimizers start afresh
+    _step(c, 5)
+    assert c.optimizer_state()["steps"] == [1, 1]
+
+
+@pytest.mark.gpu
+def test_fused_set_hyper_reaches_the_next_update():
+    _need_gpu()
+    actor, critic = KEYS[:8], CRITIC_KEYS
+    a = _fixture_agent(max_batch=64)
+    before = a.state_dict()
+    a.set_hyper(actor_lr=0.0)
+    _step(a, 1)
+    after = a.state_dict()
+    assert not any(_changed(before, after, actor)) and all(_changed(before, after, critic[::2]))
+    a.set_hyper(actor_lr=FX.HYPER["actor_lr"], critic_lr=0.0, tau=0.0)
+    before, target = after, a.optimizer_state()["target"]
+    _step(a, 2)
+    after = a.state_dict()
+    assert not any(_changed(before, after, critic)) and all(_changed(before, after, actor[::2]))
+    assert not any(_changed(target, a.optimizer_state()["target"], critic))
+    with pytest.raises(TypeError):
+        a.set_hyper(beta=0.5)
+
+
+@pytest.mark.gpu
+def test_fused_sync_target():
+    _need_gpu()
+    a = _fixture_agent(max_batch=64)
+    for u in (1, 2):
+        _step(a, u)
+    online, target = a.state_dict(), a.optimizer_state()["target"]
+    assert all(_changed(online, target, CRITIC_KEYS[::2]))                   # tau = 0.005: the target lags behind
+    a.sync_target(decay=1)
+    assert not any(_changed(target, a.optimizer_state()["target"], CRITIC_KEYS))
+    a.sync_target(decay=0)
+    assert not any(_changed(online, a.optimizer_state()["target"], CRITIC_KEYS))
+    a.sync_target(decay=1)
+    assert not any(_changed(online, a.optimizer_state()["target"], CRITIC_KEYS))
+    after = a.state_dict()
+    assert not any(_changed(online, after, KEYS))
