@@ -5,7 +5,10 @@ robot with the stochastic actor (collect_continuous on an auto_reset env) altern
 actor the simulator uses being the one the learner has just updated (learner.policy).
 
 Usage: python examples/train_sac.py [--num-envs 4096] [--iters 200] [--collect-steps 1] [--utd 4] [--eval-every 50] [--out sac.pt]
---utd: updates per control step (the reference does one update of 256 rows per transition of its single robot)."""
+                                    [--checkpoint DIR [--resume]]
+--utd: updates per control step (the reference does one update of 256 rows per transition of its single robot).
+--checkpoint DIR: at every evaluation the whole run is written to DIR -- learner.pt (weights and optimizer state), memory.npz (the
+replay memory) and env.pt (env.state_dict(): every robot mid-episode) -- and --resume picks the run up from there."""
 import argparse
 import os
 import sys
@@ -17,6 +20,24 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from paddlerobotics_amd.env import make_env  # noqa: E402
 from paddlerobotics_amd.replay import DeviceReplayMemory, collect_continuous  # noqa: E402
 from paddlerobotics_amd.sac import DeviceSAC  # noqa: E402
+
+
+def _cpu(x):
+    if torch.is_tensor(x):
+        return x.cpu()
+    if isinstance(x, dict):
+        return {k: _cpu(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_cpu(v) for v in x)
+    return x
+
+
+def save_checkpoint(path, it, learner, rpm, env):
+    os.makedirs(path, exist_ok=True)
+    torch.save({"iter": it, "model": _cpu(dict(learner.state_dict())), "optimizer": _cpu(learner.optimizer_state())},
+               os.path.join(path, "learner.pt"))
+    rpm.save(os.path.join(path, "memory.npz"))
+    torch.save(env.state_dict(), os.path.join(path, "env.pt"))
 
 
 def main():
@@ -32,17 +53,31 @@ def main():
     ap.add_argument("--eval-steps", type=int, default=200)
     ap.add_argument("--out", type=str, default="sac.pt")
     ap.add_argument("--device", type=str, default="cuda:0")
+    ap.add_argument("--checkpoint", type=str, default=None)      # directory of the run's checkpoint (off by default)
+    ap.add_argument("--resume", action="store_true")
     args = ap.parse_args()
+    if args.resume and not args.checkpoint:
+        ap.error("--resume needs --checkpoint DIR")
     env = make_env("Quadrupedal", num_envs=args.num_envs, device=args.device, auto_reset=True)
     evl = make_env("Quadrupedal", num_envs=min(args.num_envs, 256), device=args.device)
     obs_dim, act_dim = env.observation_space.shape[0], env.action_space.shape[0]
     learner = DeviceSAC(obs_dim, act_dim, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, device=args.device)
     rpm = DeviceReplayMemory(args.memory_size, obs_dim, act_dim, device=args.device)
-    env.reset()
-    collect_continuous(env, rpm, args.warmup_steps, policy=learner.policy, action_bound=0.3, mode="uniform")
+    first = 1
+    if args.resume:
+        ck = torch.load(os.path.join(args.checkpoint, "learner.pt"), map_location="cpu")
+        learner.load_state_dict(ck["model"])
+        learner.load_optimizer_state(ck["optimizer"])
+        rpm.load(os.path.join(args.checkpoint, "memory.npz"))
+        env.load_state_dict(torch.load(os.path.join(args.checkpoint, "env.pt"), map_location="cpu"))
+        first = int(ck["iter"]) + 1
+        print("resumed from %s at iteration %d, memory %d" % (args.checkpoint, first, rpm.size()))
+    else:
+        env.reset()
+        collect_continuous(env, rpm, args.warmup_steps, policy=learner.policy, action_bound=0.3, mode="uniform")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for it in range(1, args.iters + 1):
+    for it in range(first, args.iters + 1):
         collect_continuous(env, rpm, args.collect_steps, policy=learner.policy, action_bound=0.3, mode="sample")
         losses = learner.learn_from(rpm, args.batch_size, n_updates=args.utd * args.collect_steps)
         if it % args.eval_every == 0 or it == args.iters:
@@ -50,9 +85,11 @@ def main():
             ret, length = evl.rollout_policy(learner.policy, args.eval_steps, act_scale=0.3)
             dt = time.perf_counter() - t0               # the .item() calls below are this loop's only host synchronisations
             print("iter %d: %.0f control steps/s, %.0f updates/s, memory %d, critic loss %.4f, actor loss %.4f, eval return %.3f"
-                  % (it, it * args.collect_steps / dt, it * args.collect_steps * args.utd / dt, rpm.size(),
+                  % (it, (it - first + 1) * args.collect_steps / dt, (it - first + 1) * args.collect_steps * args.utd / dt, rpm.size(),
                      losses[-1, 0].item(), losses[-1, 1].item(), ret.mean().item()))
             learner.save(args.out)                      # the reference's checkpoint format: loads into its MujocoModel
+            if args.checkpoint:
+                save_checkpoint(args.checkpoint, it, learner, rpm, env)
     env.close()
     evl.close()
 

@@ -1,5 +1,6 @@
 """ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h, include/etgsim_terminal.h,
-include/etgsim_render.h, include/etgsim_sac.h and include/etgsim_bc.h (paddlerobotics_amd/csrc/libetgsim.so).
+include/etgsim_render.h, include/etgsim_sac.h, include/etgsim_bc.h and include/etgsim_snapshot.h
+(paddlerobotics_amd/csrc/libetgsim.so).
 
 There is no CPU fallback: if the library is missing this module raises, and if no HIP
 device is visible etg_create() fails with ETG_ERR_NO_DEVICE.
@@ -33,11 +34,22 @@ SAC_SYMBOLS = ["etg_sac_create", "etg_sac_destroy", "etg_sac_set_hyper", "etg_sa
 # ... and include/etgsim_bc.h
 BC_SYMBOLS = ["etg_bc_create", "etg_bc_destroy", "etg_bc_set_hyper", "etg_bc_load", "etg_bc_store", "etg_bc_load_opt",
               "etg_bc_store_opt", "etg_bc_set_teacher", "etg_bc_learn", "etg_bc_learn_replay", "etg_bc_grads", "etg_bc_sync_policy"]
+# ... and include/etgsim_snapshot.h
+SNAPSHOT_SYMBOLS = ["etg_snapshot_row_bytes", "etg_snapshot_save", "etg_snapshot_restore"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 
 class EtgError(RuntimeError):
     pass
+
+
+class EtgSnapshotHeader(C.Structure):
+    """include/etgsim_snapshot.h: what a restore checks, and the handle's scalars"""
+    _fields_ = [("magic", C.c_uint32), ("format", C.c_int32), ("abi_version", C.c_int32), ("row_bytes", C.c_int32),
+                ("layout_fp", C.c_uint64), ("config_fp", C.c_uint64), ("num_envs", C.c_int32), ("n", C.c_int32),
+                ("whole", C.c_int32), ("hf_bands", C.c_int32), ("push_calls", C.c_uint64), ("obs_calls", C.c_uint32),
+                ("noise_call", C.c_uint32), ("was_reset", C.c_uint8), ("fext_set", C.c_uint8), ("push_on", C.c_uint8),
+                ("all_cached", C.c_uint8), ("strength_on", C.c_uint8), ("next_dyn", C.c_uint8), ("pad_", C.c_uint8 * 2)]
 
 
 def lib_path():
@@ -98,6 +110,9 @@ def load():
     lib.etg_step_autoreset_terminal.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_extra_sensors_terminal.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.etg_render.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.etg_snapshot_row_bytes.argtypes = [vp]
+    lib.etg_snapshot_save.argtypes = [vp, vp, i32, vp, C.POINTER(EtgSnapshotHeader), vp]
+    lib.etg_snapshot_restore.argtypes = [vp, vp, i32, vp, C.POINTER(EtgSnapshotHeader), vp]
     lib.etg_sac_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     lib.etg_sac_destroy.argtypes = [vp]
     lib.etg_sac_set_hyper.argtypes = [vp] + [C.c_double] * 5

@@ -2111,6 +2111,9 @@ ETG_INSTP4(k_rollout_policy4, true, 3, 4, 5, 6, 7, 1, ETG_ARGS_POLICY)
 #if ETG_TU_HOST
 #include "render_core.h"
 #include "../../include/etgsim_render.h"
+#include "snapshot_core.h"
+#include "../../include/etgsim_snapshot.h"
+#include <string.h>
 
 // ====================================================================== C ABI
 using namespace etg;
@@ -3007,6 +3010,173 @@ extern "C" int etg_set_state(EtgHandle* h, const float* state, void* stream) {
   if (!state) return fail(ETG_ERR_BAD_ARG, "etg_set_state: null");
   hipLaunchKernelGGL(k_set_state, dim3(grid_for(h)), dim3(BLOCK), 0, (hipStream_t)stream, h->K, h->D, state);
   HIP_TRY(hipGetLastError());
+  return ETG_OK;
+}
+
+// ---- snapshots (include/etgsim_snapshot.h): the handle's persistent per-robot arrays as the segments of a record, in the order
+// of etg_create's allocation table followed by etg_prepare_next_dynamics's; the kernel is etg_snapshot.hip's.  Scratch, not in a
+// record: tmp_obs / tmp_reward / tmp_done (sinks of etg_rollout_openloop), nx_base / nx_leg / nx_ring / nx_cache_ok / nx_mask
+// (the state the prepared settle runs on, dead when etg_prepare_next_dynamics returns), wave_cycles, cached_report.
+static snapshot::Table snapshot_table(const EtgHandle* h) {
+  snapshot::Table T;
+  const DevState& D = h->D;
+  int off = snapshot::kHeadWords, n = 0;
+  auto add = [&](void* p, int rows, int per, int bytes) {
+    T.seg[n++] = snapshot::Seg{p, off, rows, per, bytes};
+    off += rows * per;
+  };
+  add(D.base, BS_N, 1, 0);          add(D.leg, LG_N, 4, 0);             add(D.ctl, CT_N, 1, 0);
+  add(D.ictl, IC_N, 1, 0);          add(D.legctl, LC_N, 4, 0);          add(D.etgp, EP_N, 1, 0);
+  add(D.par, PR_N, 4, 0);           add(D.ring, RING * 8, 4, 0);        add(D.dyn, 1, ETG_DYN_DIM, 0);
+  add(D.cache_base, BS_N, 1, 0);    add(D.cache_leg, LG_N, 4, 0);       add(D.cache_ring, RING * 8, 4, 0);
+  add(D.cache_ok, 1, 1, 1);         add(D.reset_off, 2, 1, 0);          add(D.cache_off, FIN_ROWS, 1, 0);
+  add(h->NX.par, PR_N, 4, 0);       add(h->NX.dyn, 1, ETG_DYN_DIM, 0);  add(h->NX.ok, 1, 1, 1);
+  static_assert(18 <= snapshot::kMaxSegs, "snapshot::Table is too small");
+  T.nseg = n;
+  T.row_words = (off + 3) / 4 * 4;
+  T.n_env = h->N;
+  return T;
+}
+static uint64_t snapshot_mix(uint64_t a, uint64_t v) { return (a ^ v) * 0x100000001B3ull; }   // FNV-1a over 64-bit words
+static uint64_t snapshot_mix(uint64_t a, float v) { uint32_t u; memcpy(&u, &v, 4); return snapshot_mix(a, (uint64_t)u); }
+// the layout constants: every segment's place and shape, and the row constants whose order inside a segment could move
+static uint64_t snapshot_layout_fp(const snapshot::Table& T) {
+  uint64_t a = 0xCBF29CE484222325ull;
+  for (int s = 0; s < T.nseg; s++)
+    for (int v : {T.seg[s].off, T.seg[s].rows, T.seg[s].per, T.seg[s].bytes}) a = snapshot_mix(a, (uint64_t)v);
+  for (int v : {T.row_words, (int)RING, (int)CT_RET, (int)CT_FEXT, (int)CT_PUSH, (int)IC_TICK, (int)IC_OBS_CALL, (int)LC_LAST_FOOT_X,
+                (int)PR_DERIVED, (int)PR_STR, (int)FIN_OBS, (int)FIN_OK, (int)ETG_OBS_DIM, (int)ETG_DYN_DIM})
+    a = snapshot_mix(a, (uint64_t)v);
+  return a;
+}
+// the configuration that gives a record its meaning (the lane mapping is not part of it: both share the layout)
+static uint64_t snapshot_config_fp(const KCfg& K) {
+  uint64_t a = 0xCBF29CE484222325ull;
+  for (int v : {K.action_repeat, K.settle_ticks, K.motor_mode, K.enable_filter, K.enable_interp, K.pd_n, K.knee, K.etg_on, K.terrain,
+                K.terrain ? K.hf_nx : 0, K.terrain ? K.hf_ny : 0, K.terrain ? K.hf_bands : 0})
+    a = snapshot_mix(a, (uint64_t)(uint32_t)v);
+  for (float v : {K.dt, K.etg_dt, K.pd_a, K.fb[0], K.fb[1], K.fb[2], K.fa[0], K.fa[1], K.fa[2], K.terrain ? K.hf_cell : 0.0f,
+                  K.terrain ? K.hf_x0 : 0.0f, K.terrain ? K.hf_y0 : 0.0f})
+    a = snapshot_mix(a, v);
+  return a;
+}
+// the ids of a call on the host (empty for env_ids == NULL), each checked against [0, N)
+static int snapshot_ids(const char* fn, EtgHandle* h, const int32_t* env_ids, int n, hipStream_t s, std::vector<int32_t>& ids) {
+  ids.clear();
+  if (!env_ids) return ETG_OK;
+  ids.resize(n);
+  HIP_TRY(hipMemcpyAsync(ids.data(), env_ids, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int i = 0; i < n; i++)
+    if (ids[i] < 0 || ids[i] >= h->N) return fail(ETG_ERR_BAD_ARG, std::string(fn) + ": env id outside [0, N)");
+  return ETG_OK;
+}
+
+extern "C" int etg_snapshot_row_bytes(EtgHandle* h) {
+  if (!h) return fail(ETG_ERR_BAD_ARG, "etg_snapshot_row_bytes: null handle");
+  return snapshot_table(h).row_words * 4;
+}
+
+extern "C" int etg_snapshot_save(EtgHandle* h, const int32_t* env_ids, int n, void* rows, EtgSnapshotHeader* hdr, void* stream) {
+  if (!h) return fail(ETG_ERR_BAD_ARG, "etg_snapshot_save: null handle");
+  HIP_TRY(hipSetDevice(h->device));
+  if (!rows || !hdr) return fail(ETG_ERR_BAD_ARG, "etg_snapshot_save: null argument");
+  if ((uintptr_t)rows % 16) return fail(ETG_ERR_BAD_ARG, "etg_snapshot_save: rows must be 16-byte aligned");
+  if (env_ids ? (n < 1 || n > (1 << 20)) : n != h->N)
+    return fail(ETG_ERR_BAD_ARG, "etg_snapshot_save: n must be N without env_ids, 1..1048576 with them");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> ids;
+  if (int rc = snapshot_ids("etg_snapshot_save", h, env_ids, n, s, ids)) return rc;
+  refresh_all_cached(h);
+  const snapshot::Table T = snapshot_table(h);
+  HIP_TRY(etg_snapshot_launch(T, env_ids, n, (uint32_t*)rows, 0, s));
+  memset(hdr, 0, sizeof(*hdr));
+  hdr->magic = ETG_SNAPSHOT_MAGIC;
+  hdr->format = ETG_SNAPSHOT_FORMAT;
+  hdr->abi_version = etg_version();
+  hdr->row_bytes = T.row_words * 4;
+  hdr->layout_fp = snapshot_layout_fp(T);
+  hdr->config_fp = snapshot_config_fp(h->K);
+  hdr->num_envs = h->N;
+  hdr->n = n;
+  hdr->whole = env_ids ? 0 : 1;
+  hdr->hf_bands = h->K.hf_bands;
+  hdr->push_calls = h->push_calls;
+  hdr->obs_calls = h->obs_calls;
+  hdr->noise_call = h->K.noise_call;
+  hdr->was_reset = h->was_reset; hdr->fext_set = h->fext_set; hdr->push_on = h->push_on; hdr->all_cached = h->all_cached;
+  hdr->strength_on = h->K.strength_on != 0;
+  hdr->next_dyn = h->NX.par != nullptr;
+  return ETG_OK;
+}
+
+extern "C" int etg_snapshot_restore(EtgHandle* h, const int32_t* env_ids, int n, const void* rows, const EtgSnapshotHeader* hdr, void* stream) {
+  if (!h) return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: null handle");
+  HIP_TRY(hipSetDevice(h->device));
+  if (!rows || !hdr) return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: null argument");
+  if ((uintptr_t)rows % 16) return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: rows must be 16-byte aligned");
+  snapshot::Table T = snapshot_table(h);
+  if (hdr->magic != ETG_SNAPSHOT_MAGIC || hdr->format != ETG_SNAPSHOT_FORMAT)
+    return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: not a snapshot header of this format");
+  if (hdr->abi_version != etg_version()) return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: the snapshot is of another library version");
+  if (hdr->row_bytes != T.row_words * 4 || hdr->layout_fp != snapshot_layout_fp(T))
+    return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: the snapshot's record layout differs from this library's");
+  if (hdr->config_fp != snapshot_config_fp(h->K) || hdr->hf_bands != h->K.hf_bands)
+    return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: the snapshot was saved under another configuration (time step, action repeat, "
+                                 "settle ticks, motor mode, filter / interpolation, pd_latency, body_contacts or terrain)");
+  if (hdr->n < 1 || (env_ids ? (n < 1 || n > hdr->n) : (n != h->N || !hdr->whole || hdr->num_envs != h->N || hdr->n != h->N)))
+    return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: n must be 1..(records saved) with env_ids; without them the snapshot must be a "
+                                 "whole one of exactly this handle's N robots");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> ids;
+  if (int rc = snapshot_ids("etg_snapshot_restore", h, env_ids, n, s, ids)) return rc;
+  if (env_ids) {
+    std::vector<unsigned char> seen(h->N, 0);
+    for (int i = 0; i < n; i++) {
+      if (seen[ids[i]]) return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: duplicate target env id");
+      seen[ids[i]] = 1;
+    }
+    if (h->K.terrain == 1 && h->K.hf_bands > 1) {   // a record's settle cache and history belong to the band it was saved on
+      std::vector<int32_t> src(n);
+      HIP_TRY(hipMemcpy2DAsync(src.data(), sizeof(int32_t), rows, (size_t)hdr->row_bytes, sizeof(int32_t), (size_t)n, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      for (int i = 0; i < n; i++)
+        if (src[i] < 0 || src[i] % h->K.hf_bands != ids[i] % h->K.hf_bands)
+          return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: a target env id is on another heightfield band than the robot its record was saved from");
+    }
+  }
+  if (hdr->next_dyn && !h->NX.par) {   // the records carry rows for the next episodes: the arrays of etg_prepare_next_dynamics
+    const size_t N = h->N, NL = 4 * N;
+    struct { void** p; size_t bytes; } allocs[] = {
+        {(void**)&h->NX.par, PR_N * NL * 4}, {(void**)&h->NX.dyn, ETG_DYN_DIM * N * 4}, {(void**)&h->NX.ok, N},
+        {(void**)&h->nx_base, BS_N * N * 4}, {(void**)&h->nx_leg, LG_N * NL * 4}, {(void**)&h->nx_ring, (size_t)RING * 8 * NL * 4},
+        {(void**)&h->nx_cache_ok, N}, {(void**)&h->nx_mask, N}};
+    for (auto& a : allocs) {
+      if (!*a.p && hipMalloc(a.p, a.bytes) != hipSuccess) return fail(ETG_ERR_ALLOC, "etg_snapshot_restore: hipMalloc failed");
+      HIP_TRY(hipMemsetAsync(*a.p, 0, a.bytes, s));
+    }
+    T = snapshot_table(h);
+  }
+  HIP_TRY(etg_snapshot_launch(T, env_ids, n, (uint32_t*)const_cast<void*>(rows), 1, s));
+  refresh_all_cached(h);
+  h->inval_seq++;   // a count of uncached robots reported by an earlier masked reset no longer describes the arrays
+  if (!env_ids) {
+    h->push_calls = hdr->push_calls;
+    h->obs_calls = hdr->obs_calls;
+    h->K.noise_call = hdr->noise_call;
+    h->was_reset = hdr->was_reset != 0;
+    h->fext_set = hdr->fext_set != 0;
+    h->push_on = hdr->push_on != 0;
+    h->all_cached = hdr->all_cached != 0;
+    h->K.strength_on = hdr->strength_on;
+  } else {   // some robots: the others keep theirs, so a flag holds if either side needs it (all_cached: if both sides have it)
+    h->was_reset = h->was_reset || hdr->was_reset;
+    h->fext_set = h->fext_set || hdr->fext_set;
+    h->push_on = h->push_on || hdr->push_on;
+    h->all_cached = h->all_cached && hdr->all_cached;
+    h->K.strength_on = h->K.strength_on || hdr->strength_on;
+  }
+  h->K.ext_force = h->fext_set || h->push_on;
   return ETG_OK;
 }
 #endif   // ETG_TU_HOST

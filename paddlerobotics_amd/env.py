@@ -172,6 +172,28 @@ def _uniform_torque_limit(limits):
     return float(a[0])
 
 
+class EnvSnapshot:
+    """Saved robots (BatchedQuadrupedEnv.snapshot): `rows` uint8 [n, row_bytes] on the device, one record per robot
+    (include/etgsim_snapshot.h); `header`, what a restore checks plus the library handle's scalars; `env_ids` int32 [n], the robots
+    saved (None: every robot); `host`, the env's Python-side state (snapshots of every robot only)."""
+
+    def __init__(self, rows, header, env_ids=None, host=None):
+        self.rows, self.header, self.env_ids, self.host = rows, header, env_ids, host
+
+    @property
+    def row_bytes(self):
+        return int(self.header.row_bytes)
+
+    def __len__(self):
+        return int(self.rows.shape[0])
+
+    def select(self, index):
+        """the records at positions `index` (a list of record numbers) as a snapshot of their own, for restore(snap, env_ids)"""
+        idx = torch.as_tensor(index, device=self.rows.device).reshape(-1).long()
+        ids = idx.to(torch.int32) if self.env_ids is None else self.env_ids[idx]
+        return EnvSnapshot(self.rows[idx].contiguous(), self.header, ids.contiguous(), None)
+
+
 class BatchedQuadrupedEnv:
     def __init__(self, num_envs=1, device="cuda:0", task="ground", motor_control_mode=None, render=False,
                  sensor_mode=None, normal=1, dynamic_param=None, reward_param=None, ETG=1, ETG_T=0.5,
@@ -541,11 +563,13 @@ class BatchedQuadrupedEnv:
         if stdev is None:
             _lib.check(self._lib.etg_set_sensor_noise(self._h, None, C.c_uint64(0)))
             self._noise_on = False
+            self._noise_cfg = None
             return
         a = np.ascontiguousarray(stdev, dtype=np.float32)
         if a.shape != (5,):
             raise ValueError("observation_noise_stdev needs 5 values (angle, velocity, torque, rpy, rpy rate)")
         self._noise_on = bool(np.any(a != 0))
+        self._noise_cfg = (tuple(float(v) for v in a), int(seed))      # kept for snapshots (state_dict)
         _lib.check(self._lib.etg_set_sensor_noise(self._h, a.ctypes.data_as(C.c_void_p), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
 
     def set_reset_offsets(self, xy, env_ids=None):
@@ -1072,6 +1096,127 @@ class BatchedQuadrupedEnv:
         _lib.check(self._lib.etg_set_contact_impulses(self._h, _ptr(lam), self._stream()))
         self._keep_lam = lam
 
+    # ---- snapshots (include/etgsim_snapshot.h) -----------------------------------
+    # what the env keeps on the Python side between calls: its own buffers, which the library writes into (copied in place) ...
+    _HOST_BUFFERS = ("obs", "reward", "done", "info_buf", "extra")
+    # ... tensors that each call replaces (the current view, the history ring, the pending reset mask) ...
+    _HOST_VIEWS = ("_last_view", "_hist", "_last_seq", "_reset_mask")
+    # ... plain values (history head, next-dynamics bookkeeping, push settings) ...
+    _HOST_VALUES = ("_hist_head", "_nx_on", "_nx_count", "_nx_first", "_nx_refresh", "_noise_offsets", "_push_seed", "_rf_prob",
+                    "_rf_steps", "_rf_range")
+    # ... and what a setter installs in the library: "_noise_cfg" (set_sensor_noise), "simulate_finished" (set_rollout_mode)
+
+    def _host_state(self):
+        d = {}
+        for k in self._HOST_BUFFERS + self._HOST_VIEWS:
+            v = getattr(self, k, None)
+            d[k] = v.clone() if torch.is_tensor(v) else None
+        for k in self._HOST_VALUES + ("_noise_cfg", "simulate_finished"):
+            d[k] = getattr(self, k, None)
+        d["_dyn_gen"] = self._dyn_gen.get_state().clone()
+        return d
+
+    def _set_host_state(self, d):
+        for k in self._HOST_BUFFERS:
+            if d.get(k) is not None and getattr(self, k, None) is not None:
+                getattr(self, k).copy_(d[k])
+        for k in self._HOST_VIEWS:
+            setattr(self, k, None if d.get(k) is None else d[k].to(self.device).clone())
+        for k in self._HOST_VALUES:
+            setattr(self, k, d.get(k))
+        self._dyn_gen.set_state(d["_dyn_gen"].cpu())
+        noise = d.get("_noise_cfg")
+        if noise is None:
+            self.set_sensor_noise(None)
+        else:
+            self.set_sensor_noise(noise[0], seed=noise[1])
+        self.set_rollout_mode(bool(d.get("simulate_finished")))
+
+    def _ids32(self, env_ids):
+        ids = torch.as_tensor(env_ids, device=self.device)
+        ids = ids.nonzero().reshape(-1) if ids.dtype == torch.bool else ids.reshape(-1)
+        return ids.to(torch.int32).contiguous()
+
+    def snapshot(self, env_ids=None):
+        """Save robots (the reference simulator's saveState): an EnvSnapshot with one record per robot of `env_ids` (robot
+        indices or a boolean [N] mask; None: every robot) on the device -- everything the library keeps for the robot, so that
+        a robot restored from its record goes on bit for bit as this one does.  A snapshot of every robot also carries what
+        the env keeps on the Python side (observation buffers, history, the dynamics generator, noise and push settings), so
+        restore(snap) brings the whole env back."""
+        ids = None if env_ids is None else self._ids32(env_ids)
+        n = self.num_envs if ids is None else int(ids.numel())
+        rb = int(self._lib.etg_snapshot_row_bytes(self._h))
+        rows = torch.empty(max(n, 1), rb, dtype=torch.uint8, device=self.device)
+        hdr = _lib.EtgSnapshotHeader()
+        _lib.check(self._lib.etg_snapshot_save(self._h, _ptr(ids), n, _ptr(rows), C.byref(hdr), self._stream()))
+        return EnvSnapshot(rows, hdr, ids, self._host_state() if ids is None else None)
+
+    def restore(self, snap, env_ids=None):
+        """Put saved robots back (restoreState), or transplant them: record i of `snap` goes to robot env_ids[i] (default: the
+        robot it was saved from; a snapshot of every robot then restores the whole env, Python side included).  The target may
+        be another env of the same configuration -- any size, either lane mapping -- whose other robots are not touched.
+        Refused (EtgError, nothing changed): another configuration or terrain kind, ids outside [0, N) or twice, on a banded
+        heightfield a target on another band than the record's robot."""
+        if env_ids is None:
+            ids = snap.env_ids
+        else:
+            ids = self._ids32(env_ids)
+            if ids.numel() > snap.rows.shape[0]:
+                raise ValueError("restore: %d target ids for a snapshot of %d robots" % (ids.numel(), snap.rows.shape[0]))
+        rows = snap.rows.to(self.device)
+        hdr = snap.header
+        if ids is None:
+            if snap.host is not None and snap.host["obs"].shape != self.obs.shape:
+                raise ValueError("restore: the snapshot holds %d robots, this env %d (pass env_ids to transplant some)"
+                                 % (snap.host["obs"].shape[0], self.num_envs))
+            _lib.check(self._lib.etg_snapshot_restore(self._h, None, self.num_envs, _ptr(rows), C.byref(hdr), self._stream()))
+            if snap.host is not None:
+                self._set_host_state(snap.host)
+        else:
+            ids = ids.to(self.device)
+            _lib.check(self._lib.etg_snapshot_restore(self._h, _ptr(ids), int(ids.numel()), _ptr(rows), C.byref(hdr), self._stream()))
+        self._keep_snap = (rows, ids)
+
+    def _config_digest(self):
+        """what load_state_dict() compares: the library's configuration and robot model, the observation view, the terrain"""
+        import hashlib
+        h = hashlib.sha256()
+        h.update(bytes(self.cfg))
+        h.update(bytes(self.model))
+        h.update(repr((self.task, self._cols, self._xcols, self._hist_T, self._hist_dt, self._hist_mode, self.auto_reset,
+                       self._rand_dyn, self._rand_force, self._rand_dyn_scale, self.lanes_per_robot)).encode())
+        cfg = h.hexdigest()
+        t = hashlib.sha256()
+        if self._hf is not None:
+            t.update(self._hf.cpu().numpy().tobytes())
+            t.update(repr({k: (np.asarray(v).tolist() if not np.isscalar(v) else v) for k, v in sorted(self.terrain.items())
+                           if k != "heights"}).encode())
+        return cfg, t.hexdigest()
+
+    def state_dict(self):
+        """The whole env as CPU tensors and plain values (torch.save takes it): the snapshot of every robot, what the env keeps
+        on the Python side, and digests of the configuration and the heightfield that load_state_dict() checks."""
+        snap = self.snapshot()
+        host = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in snap.host.items()}
+        cfg, terrain = self._config_digest()
+        return {"rows": snap.rows.cpu(), "header": torch.frombuffer(bytearray(bytes(snap.header)), dtype=torch.uint8).clone(),
+                "host": host, "config_digest": cfg, "terrain_digest": terrain, "num_envs": self.num_envs}
+
+    def load_state_dict(self, sd):
+        """restore a state_dict() into an env made with the same arguments; ValueError when configuration or terrain differ"""
+        cfg, terrain = self._config_digest()
+        if sd.get("config_digest") != cfg:
+            raise ValueError("load_state_dict: the state was saved by an env with another configuration")
+        if sd.get("terrain_digest") != terrain:
+            raise ValueError("load_state_dict: the state was saved on another terrain")
+        hb = bytes(sd["header"].cpu().numpy().tobytes())
+        if len(hb) != C.sizeof(_lib.EtgSnapshotHeader):
+            raise ValueError("load_state_dict: not a snapshot header")
+        hdr = _lib.EtgSnapshotHeader.from_buffer_copy(hb)
+        host = {k: (v.to(self.device) if torch.is_tensor(v) and k != "_dyn_gen" else v) for k, v in sd["host"].items()}
+        self.restore(EnvSnapshot(sd["rows"].to(self.device).contiguous(), hdr, None, host))
+        torch.cuda.synchronize(self.device)
+
     # ---- camera images (include/etgsim_render.h) --------------------------------
     def render(self, env_ids=None, width=320, height=240, view_matrix=None, projection_matrix=None, depth=False,
                segmentation=False, states=None):
@@ -1163,6 +1308,18 @@ class SingleRobotEnv:
         if mode != "rgb_array":
             raise NotImplementedError("only mode='rgb_array' exists here")
         return self.batched.render([0], width, height)[0, :, :, :3].cpu().numpy()
+
+    def snapshot(self, env_ids=None):
+        return self.batched.snapshot(env_ids)
+
+    def restore(self, snap, env_ids=None):
+        return self.batched.restore(snap, env_ids)
+
+    def state_dict(self):
+        return self.batched.state_dict()
+
+    def load_state_dict(self, sd):
+        return self.batched.load_state_dict(sd)
 
     def close(self):
         self.batched.close()
