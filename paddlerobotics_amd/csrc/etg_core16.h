@@ -23,6 +23,13 @@
 
 namespace etg {
 
+// Ctx::kSweepStream: the context brings the residual-rule loop of a tick with body rows as one hand-scheduled stream
+// (GpuCtx16::pgs_body_stream); a context that does not say so (the emulation's) runs the C++ statement of the sweeps.
+template <class Ctx, class = void> struct sweep_stream_ : std::false_type {};
+template <class Ctx> struct sweep_stream_<Ctx, std::void_t<decltype(Ctx::kSweepStream)>> : std::bool_constant<Ctx::kSweepStream> {};
+// (the call goes through a template of its own: contexts without the stream never instantiate it)
+template <class Ctx, class... Args> ETG_HD void run_sweep_stream_(const Ctx& c, Args&&... args) { c.pgs_body_stream(args...); }
+
 template <class F> struct State16 {
   V3<F> p;
   F qx, qy, qz, qw;
@@ -824,6 +831,20 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
       }
       if constexpr (body) body_friction(c.qb(lam, 3));
     };
+    if constexpr (sweep_stream_<Ctx>::value && body && !joints && !pyramid) {
+      // the device build's residual-rule loop of a tick with body rows: the sweeps below, their bookkeeping (the copies, the
+      // votes, the lazy freeze, the sweep cap of sweep_and_test) included, as one hand-scheduled stream
+      // (GpuCtx16::pgs_body_stream states what sits where).  Same sweeps, same values, same count.
+      if (K.res_thr > 0.0f) {
+        F tol = F(K.res_sqrt) * iA, tol2 = F(K.res_sqrt) * iA2;
+        c.opaque(tol); c.opaque(tol2);
+        const unsigned cap = (unsigned)(K.iters > 1 ? K.iters : 1) - 1u;
+        unsigned rem = cap;
+        run_sweep_stream_(c, lam, u, u2, lam2, rem, iAe, c0e, mue, A, Ak, mk0, mk3, mt, Bn, Bt, iA2, K.body_mu, ATr, BBr, tol, tol2);
+        L.sweeps += (int)(cap - rem) + (rem != ~0u ? 1 : 0);      // (rem wraps on the sweep that reaches the cap)
+        return;
+      }
+    }
     if (K.res_thr > 0.0f) {
       // EtgConfig.solver_residual (etgsim.h): sweep until the robot's largest squared row residual
       // ((lam - lam at the start of the sweep) * A_rr)^2 is <= the threshold, K.iters sweeps at most.

@@ -901,6 +901,167 @@ struct GpuCtx16 {
     switch (lp) { case 0: ETG_PAIRB(1, 2); break; case 1: ETG_PAIRB(5, 6); break; case 2: ETG_PAIRB(9, 10); break; default: ETG_PAIRB(13, 14); break; }
 #undef ETG_PAIRB
   }
+#if !defined(ETG_SWEEP_BOOKKEEPING_OUTSIDE) && !defined(ETG_NO_ASM_SWEEP) && !defined(ETG_EAGER_FREEZE)
+  // ---- the residual-rule loop of a tick with body rows as ONE scheduled stream (etg_core16.h: solve; kSweepStream): the rows of
+  // pgs_normals_body2, pgs_tangents_disc2 and pgs_pair_body, instruction for instruction, with everything sweep_and_test does
+  // AROUND them -- copies, grip selects, the body pairs' constants and leg tests, the residual votes, the lazy freeze, the
+  // sweep cap -- placed by hand.  A lone wave pays an issue slot for every instruction, an s_nop included, so whatever fits a
+  // wait state of the rows is free and the rest is made as short as it goes:
+  //   * the values at the start of the sweep are not copied: they STAY in lam / u / u2 / lam2 and the sweep works on w / wu /
+  //     wu2 / w2 -- row 0 commits with a three-operand v_fma into w, `wu = u` sits in row 0's wait state, `w2 = lam2` in a
+  //     wait state of the first foot pair (wu2 = u2 is the one copy that costs a slot);
+  //   * the ten wait states of the foot pairs hold: the per-robot mask of the PREVIOUS sweep's votes (`live`: three
+  //     instructions on the wave mask, which the previous sweep left in vcc), the body pairs' grip compare, limit and selects,
+  //     the fold of the grip mask to one bit group per leg, and the first residual difference;
+  //   * a leg's test is one s_and_b32 (it sets SCC) and a branch;
+  //   * the residual masks are taken on the un-restored impulses and AND-ed with `live` as scalars (a restored robot's
+  //     difference is 0 > tol: false -- the same votes), the AND sets SCC for the exit branch; the sweep cap counts `rem`
+  //     down (s_sub_u32 borrows on the sweep that reaches the cap);
+  //   * the lazy freeze is four selects on `live` at the end of the sweep.
+  // 123 issue slots per sweep without a loaded body leg, 127 + 16 per loaded leg with (sweep_and_test around the three
+  // blocks: 152 + 16 per leg).  Every arithmetic instruction has the operands it has there and every register sees its updates
+  // in the same order: the results are the same bit for bit.  fl / fh: this lane's robot (16-lane row) in the low / high half of
+  // a wave mask.  rem: K.iters - 1 on entry (at least 0); on return K.iters - 1 - (sweeps - 1), or ~0u after the cap.
+  __device__ __forceinline__ void pgs_body_stream(float& lam, float& u, float& u2, float& lam2, unsigned& rem, float iA, float c0, float mue,
+                                                  const float (&A)[4][3], const float* Ak, const float* mk0, const float* mk3, const float* mt,
+                                                  const float* bn, const float* bt, float iA2, float body_mu, const float (&AT)[4][2],
+                                                  const float (&BB)[4][2], float tol, float tol2) const {
+    const unsigned row16 = 0xFFFFu << (tid & 16);
+    const unsigned fl = (tid & 32) ? 0u : row16, fh = (tid & 32) ? row16 : 0u;
+    float w, wu, wu2, w2, t, dA, dB, lnq, lbn, iAg, limg, lim, lc, sq, sc, iA2g, lim2g, rr;
+    unsigned x, gm, tmp;
+    unsigned long long live, mv, sa;
+#ifdef ETG_FORCE_BODY
+#define ETG_SGM "s_or_b32 %[gm], -1, -1\n"
+#else
+#define ETG_SGM "s_or_b32 %[gm], vcc_lo, vcc_hi\n"            /* a leg's lanes at the same bits of both halves; SCC = any  */
+#endif
+#define ETG_SU2(D, LP, BOP) "v_fmac_f32_dpp %[wu2], %[" D "], %[" BOP "] row_newbcast:" #LP ETG_DPPC
+#define ETG_SROW(D, LP, AOP, MOP, FILL)                                              \
+    "v_fma_f32 %[t], -%[wu], %[iA], %[c0]\n"                                         \
+    "v_max_f32_e64 %[" D "], -%[w], %[t]\n"                                          \
+    "v_fmac_f32_e32 %[w], %[" MOP "], %[" D "]\n"                                    \
+    FILL                                                                             \
+    "v_fmac_f32_dpp %[wu], %[" D "], %[" AOP "] row_newbcast:" #LP ETG_DPPC
+#define ETG_SPAIR(D, R1, R2, A1, A2, MOP, F1, F2, F3)                                \
+    "v_fma_f32 %[lc], -%[wu], %[iAg], %[w]\n"                                        \
+    "v_fmaak_f32 %[sq], %[lc], %[lc], 0x0da24260\n"                                  \
+    F1                                                                               \
+    "v_add_f32_dpp %[sq], %[sq], %[sq] quad_perm:[0,2,1,3]" ETG_DPPC                 \
+    "v_rsq_f32_e32 %[sq], %[sq]\n"                                                   \
+    F2                                                                               \
+    "v_mul_f32_e32 %[sc], %[limg], %[sq]\n"                                          \
+    "v_min_f32_e32 %[sc], 1.0, %[sc]\n"                                              \
+    "v_fma_f32 %[" D "], %[lc], %[sc], -%[w]\n"                                      \
+    "v_fmac_f32_e32 %[w], %[" MOP "], %[" D "]\n"                                    \
+    F3                                                                               \
+    "v_fmac_f32_dpp %[wu], %[" D "], %[" A1 "] row_newbcast:" #R1 ETG_DPPC           \
+    "v_fmac_f32_dpp %[wu], %[" D "], %[" A2 "] row_newbcast:" #R2 ETG_DPPC
+#define ETG_SLEG(LP, LEGBITS, R1, R2, MOP)                                           \
+    "s_and_b32 %[tmp], %[gm], " LEGBITS "\n"                                         \
+    "s_cbranch_scc0 .Letg_sw_leg" #LP "_%=\n"                                        \
+    "v_fma_f32 %[lc], -%[wu2], %[iA2g], %[w2]\n"                                     \
+    "v_fmaak_f32 %[sq], %[lc], %[lc], 0x0da24260\n"                                  \
+    "s_nop 1\n"                                                                      \
+    "v_add_f32_dpp %[sq], %[sq], %[sq] quad_perm:[0,2,1,3]" ETG_DPPC                 \
+    "v_rsq_f32_e32 %[sq], %[sq]\n"                                                   \
+    "s_nop 0\n"                                                                      \
+    "v_mul_f32_e32 %[sc], %[lim2g], %[sq]\n"                                         \
+    "v_min_f32_e32 %[sc], 1.0, %[sc]\n"                                              \
+    "v_fma_f32 %[dA], %[lc], %[sc], -%[w2]\n"                                        \
+    "v_fmac_f32_e32 %[w2], %[" MOP "], %[dA]\n"                                      \
+    "s_nop 0\n"                                                                      \
+    "v_fmac_f32_dpp %[wu], %[dA], %[at" #LP "0] row_newbcast:" #R1 ETG_DPPC          \
+    "v_fmac_f32_dpp %[wu2], %[dA], %[bb" #LP "0] row_newbcast:" #R1 ETG_DPPC         \
+    "v_fmac_f32_dpp %[wu], %[dA], %[at" #LP "1] row_newbcast:" #R2 ETG_DPPC          \
+    "v_fmac_f32_dpp %[wu2], %[dA], %[bb" #LP "1] row_newbcast:" #R2 ETG_DPPC         \
+    ".Letg_sw_leg" #LP "_%=:\n"
+    asm volatile(
+        "s_mov_b64 vcc, -1\n"                                        /* votes "before the first sweep": nobody is frozen      */
+        ".Letg_sw_top_%=:\n"
+        /* ---- normal rows: the feet's, then the body's (pgs_normals_body2) */
+        "v_mov_b32_e32 %[wu2], %[u2]\n"
+        "v_fma_f32 %[t], -%[u], %[iA], %[c0]\n"
+        "v_max_f32_e64 %[dA], -%[lam], %[t]\n"
+        "v_fma_f32 %[w], %[m0], %[dA], %[lam]\n"                     /* row 0 commits into the working register               */
+        "v_mov_b32_e32 %[wu], %[u]\n"
+        "v_fmac_f32_dpp %[wu], %[dA], %[a0] row_newbcast:0" ETG_DPPC
+        ETG_SROW("dB", 4, "a1", "m1", ETG_SU2("dA", 0, "b0"))
+        ETG_SROW("dA", 8, "a2", "m2", ETG_SU2("dB", 4, "b1"))
+        ETG_SROW("dB", 12, "a3", "m3", ETG_SU2("dA", 8, "b2"))
+        ETG_SROW("dA", 3, "k0", "n0", ETG_SU2("dB", 12, "b3"))
+        ETG_SROW("dB", 7, "k1", "n1", ETG_SU2("dA", 3, "b4"))
+        ETG_SROW("dA", 11, "k2", "n2", ETG_SU2("dB", 7, "b5"))
+        ETG_SROW("dB", 15, "k3", "n3", ETG_SU2("dA", 11, "b6"))
+        ETG_SU2("dB", 15, "b7")
+        /* ---- the feet's grip: friction constants of a foot without load are the identity's (pgs_tangents_disc) */
+        "v_mov_b32_dpp %[lnq], %[w] quad_perm:[0,0,0,0]" ETG_DPPC
+        "v_mov_b32_dpp %[lbn], %[w] quad_perm:[3,3,3,3]" ETG_DPPC
+        "v_cmp_lt_f32_e64 %[sa], 0, %[lnq]\n"
+        "v_mul_f32_e32 %[lim], %[mue], %[lnq]\n"
+        "v_cndmask_b32_e64 %[iAg], 0, %[iA], %[sa]\n"
+        "v_cndmask_b32_e64 %[limg], %[big], %[lim], %[sa]\n"
+        /* ---- the feet's friction pairs (pgs_tangents_disc2); in their wait states: live, the body pairs' constants, gm, rr */
+        ETG_SPAIR("dA", 1, 2, "a01", "a02", "t0",
+                  "v_and_b32_e32 %[x], vcc_lo, %[fl]\n" "v_and_or_b32 %[x], vcc_hi, %[fh], %[x]\n",
+                  "v_cmp_ne_u32_e64 %[live], 0, %[x]\n",
+                  "v_mov_b32_e32 %[w2], %[lam2]\n")
+        ETG_SPAIR("dB", 5, 6, "a11", "a12", "t1", ETG_SU2("dA", 1, "e0") ETG_SU2("dA", 2, "e1"),
+                  "v_cmp_lt_f32_e32 vcc, 0, %[lbn]\n",
+                  "v_mul_f32_e32 %[lim], %[bmu], %[lbn]\n")
+        ETG_SPAIR("dA", 9, 10, "a21", "a22", "t2", ETG_SU2("dB", 5, "e2") ETG_SU2("dB", 6, "e3"),
+                  "v_cndmask_b32_e32 %[iA2g], 0, %[iA2], vcc\n",
+                  "v_cndmask_b32_e32 %[lim2g], %[big], %[lim], vcc\n")
+        ETG_SPAIR("dB", 13, 14, "a31", "a32", "t3", ETG_SU2("dA", 9, "e4") ETG_SU2("dA", 10, "e5"),
+                  ETG_SGM,
+                  "v_sub_f32_e32 %[rr], %[w], %[lam]\n")
+        ETG_SU2("dB", 13, "e6") ETG_SU2("dB", 14, "e7")
+        "v_cmp_gt_f32_e64 %[mv], |%[rr]|, %[tol]\n"
+        "s_cbranch_scc0 .Letg_sw_nf_%=\n"                            /* no body normal of the wave carries load               */
+        /* ---- the body contacts' friction pairs (pgs_pair_body), legs without a loaded contact in the wave skipped */
+        ETG_SLEG(0, "0x000f000f", 1, 2, "t0")
+        ETG_SLEG(1, "0x00f000f0", 5, 6, "t1")
+        ETG_SLEG(2, "0x0f000f00", 9, 10, "t2")
+        ETG_SLEG(3, "0xf000f000", 13, 14, "t3")
+        "v_sub_f32_e32 %[rr], %[w2], %[lam2]\n"
+        "v_cmp_gt_f32_e64 %[sa], |%[rr]|, %[tol2]\n"
+        "s_or_b64 %[mv], %[mv], %[sa]\n"
+        "v_cndmask_b32_e64 %[lam2], %[lam2], %[w2], %[live]\n"
+        ".Letg_sw_nf_%=:\n"
+        /* ---- a robot that had converged before this sweep keeps its values; the votes of the others; exit tests */
+        "v_cndmask_b32_e64 %[lam], %[lam], %[w], %[live]\n"
+        "v_cndmask_b32_e64 %[u], %[u], %[wu], %[live]\n"
+        "v_cndmask_b32_e64 %[u2], %[u2], %[wu2], %[live]\n"
+        "s_and_b64 vcc, %[mv], %[live]\n"
+        "s_cbranch_scc0 .Letg_sw_end_%=\n"                           /* no robot of the wave moved                            */
+        "s_sub_u32 %[rem], %[rem], 1\n"
+        "s_cbranch_scc0 .Letg_sw_top_%=\n"                           /* (borrow: that was sweep K.iters)                      */
+        ".Letg_sw_end_%=:\n"
+        : [lam] "+&v"(lam), [u] "+&v"(u), [u2] "+&v"(u2), [lam2] "+&v"(lam2), [rem] "+&s"(rem), [w] "=&v"(w), [wu] "=&v"(wu), [wu2] "=&v"(wu2),
+          [w2] "=&v"(w2), [t] "=&v"(t), [dA] "=&v"(dA), [dB] "=&v"(dB), [lnq] "=&v"(lnq), [lbn] "=&v"(lbn), [iAg] "=&v"(iAg), [limg] "=&v"(limg),
+          [lim] "=&v"(lim), [lc] "=&v"(lc), [sq] "=&v"(sq), [sc] "=&v"(sc), [iA2g] "=&v"(iA2g), [lim2g] "=&v"(lim2g), [rr] "=&v"(rr), [x] "=&v"(x),
+          [gm] "=&s"(gm), [tmp] "=&s"(tmp), [live] "=&s"(live), [mv] "=&s"(mv), [sa] "=&s"(sa)
+        : [iA] "v"(iA), [c0] "v"(c0), [mue] "v"(mue), [big] "v"(1e30f), [a0] "v"(A[0][0]), [a1] "v"(A[1][0]), [a2] "v"(A[2][0]), [a3] "v"(A[3][0]),
+          [m0] "v"(mk0[0]), [m1] "v"(mk0[1]), [m2] "v"(mk0[2]), [m3] "v"(mk0[3]),
+          [k0] "v"(Ak[0]), [k1] "v"(Ak[1]), [k2] "v"(Ak[2]), [k3] "v"(Ak[3]),
+          [n0] "v"(mk3[0]), [n1] "v"(mk3[1]), [n2] "v"(mk3[2]), [n3] "v"(mk3[3]),
+          [b0] "v"(bn[0]), [b1] "v"(bn[1]), [b2] "v"(bn[2]), [b3] "v"(bn[3]), [b4] "v"(bn[4]), [b5] "v"(bn[5]), [b6] "v"(bn[6]), [b7] "v"(bn[7]),
+          [a01] "v"(A[0][1]), [a02] "v"(A[0][2]), [a11] "v"(A[1][1]), [a12] "v"(A[1][2]), [a21] "v"(A[2][1]), [a22] "v"(A[2][2]),
+          [a31] "v"(A[3][1]), [a32] "v"(A[3][2]), [t0] "v"(mt[0]), [t1] "v"(mt[1]), [t2] "v"(mt[2]), [t3] "v"(mt[3]),
+          [e0] "v"(bt[0]), [e1] "v"(bt[1]), [e2] "v"(bt[2]), [e3] "v"(bt[3]), [e4] "v"(bt[4]), [e5] "v"(bt[5]), [e6] "v"(bt[6]), [e7] "v"(bt[7]),
+          [iA2] "v"(iA2), [bmu] "s"(body_mu), [at00] "v"(AT[0][0]), [at01] "v"(AT[0][1]), [at10] "v"(AT[1][0]), [at11] "v"(AT[1][1]),
+          [at20] "v"(AT[2][0]), [at21] "v"(AT[2][1]), [at30] "v"(AT[3][0]), [at31] "v"(AT[3][1]),
+          [bb00] "v"(BB[0][0]), [bb01] "v"(BB[0][1]), [bb10] "v"(BB[1][0]), [bb11] "v"(BB[1][1]),
+          [bb20] "v"(BB[2][0]), [bb21] "v"(BB[2][1]), [bb30] "v"(BB[3][0]), [bb31] "v"(BB[3][1]),
+          [tol] "v"(tol), [tol2] "v"(tol2), [fl] "v"(fl), [fh] "v"(fh)
+        : "vcc", "scc");
+#undef ETG_SGM
+#undef ETG_SU2
+#undef ETG_SROW
+#undef ETG_SPAIR
+#undef ETG_SLEG
+  }
+#endif
 #undef ETG_DPPC
   // every value that later feeds fmac_rbcast / fmac_qb as the broadcast source passes through here: the
   // asm "modifies" them, so their producers are ordered before it and the DPP reads after it
@@ -994,6 +1155,12 @@ template <bool FLAT, bool KNEE = false, bool PLAIN = false, bool SLOTB_LDS = fal
   static constexpr bool kAsmSweep = false;
 #else
   static constexpr bool kAsmSweep = true;     // pgs_normals / pgs_tangents_disc: the hand-scheduled sweep
+#endif
+  // -DETG_SWEEP_BOOKKEEPING_OUTSIDE (A/B build variant): the round-7 form, sweep_and_test's own statements around the asm blocks
+#if defined(ETG_NO_ASM_SWEEP) || defined(ETG_SWEEP_BOOKKEEPING_OUTSIDE) || defined(ETG_EAGER_FREEZE)
+  static constexpr bool kSweepStream = false;
+#else
+  static constexpr bool kSweepStream = true;  // pgs_body_stream: the body tail's residual-rule loop, bookkeeping included
 #endif
 };
 

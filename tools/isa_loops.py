@@ -1,4 +1,5 @@
-"""Loops of one kernel in a disassembled gfx950 code object: every backward branch with the instruction mix of its body.
+"""Loops of one kernel in a disassembled gfx950 code object: every backward branch with the instruction mix of its body and
+its issue slots (one per instruction, N + 1 for an s_nop N: what a lone wave pays for the body from end to end).
 usage: python tools/isa_loops.py <disassembly.s> <mangled-kernel-name> [--dump START END]"""
 import collections
 import re
@@ -38,6 +39,11 @@ def kind(t):
     return "other"
 
 
+def slots(t):
+    m = re.match(r"s_nop (\d+)", t)
+    return int(m.group(1)) + 1 if m else 1
+
+
 def main():
     ins = kernel_lines(sys.argv[1], sys.argv[2])
     print(len(ins), "instructions")
@@ -58,7 +64,7 @@ def main():
         if tgt < a:
             body = [x for x in ins if tgt <= x[0] <= a]
             c = collections.Counter(kind(x[1]) for x in body)
-            print("loop %x..%x  %5d instr  %s" % (tgt, a, len(body), dict(c)))
+            print("loop %x..%x  %5d instr  %5d slots  %s" % (tgt, a, len(body), sum(slots(x[1]) for x in body), dict(c)))
 
 
 if __name__ == "__main__":
