@@ -4,8 +4,10 @@ evaluation :182-211) on one GPU with nothing waiting for the host: warm-up with 
 robot with the stochastic actor (collect_continuous on an auto_reset env) alternating with learn_from on the replay memory, the
 actor the simulator uses being the one the learner has just updated (learner.policy).
 
-Usage: python examples/train_sac.py [--num-envs 4096] [--iters 200] [--collect-steps 1] [--utd 4] [--eval-every 50] [--out sac.pt]
-                                    [--checkpoint DIR [--resume]]
+Usage: python examples/train_sac.py [--num-envs 4096] [--iters 200] [--collect-steps 1] [--collect-chunk 0] [--utd 4]
+                                    [--eval-every 50] [--out sac.pt] [--checkpoint DIR [--resume]]
+--collect-chunk K: the --collect-steps control steps of an iteration run K to a launch (env.collect_policy) instead of one
+launch per step; 0 (the default) is the per-step path.
 --utd: updates per control step (the reference does one update of 256 rows per transition of its single robot).
 --checkpoint DIR: at every evaluation the whole run is written to DIR -- learner.pt (weights and optimizer state), memory.npz (the
 replay memory) and env.pt (env.state_dict(): every robot mid-episode) -- and --resume picks the run up from there."""
@@ -45,6 +47,7 @@ def main():
     ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--collect-steps", type=int, default=1)
+    ap.add_argument("--collect-chunk", type=int, default=0)      # control steps per collection launch; 0: one launch per step
     ap.add_argument("--utd", type=int, default=4)
     ap.add_argument("--warmup-steps", type=int, default=4)       # control steps of uniform actions (WARMUP_STEPS, train.py:33)
     ap.add_argument("--batch-size", type=int, default=256)       # BATCH_SIZE, train.py:37
@@ -78,7 +81,8 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(first, args.iters + 1):
-        collect_continuous(env, rpm, args.collect_steps, policy=learner.policy, action_bound=0.3, mode="sample")
+        collect_continuous(env, rpm, args.collect_steps, policy=learner.policy, action_bound=0.3, mode="sample",
+                           chunk=args.collect_chunk if args.collect_chunk > 0 else None)
         losses = learner.learn_from(rpm, args.batch_size, n_updates=args.utd * args.collect_steps)
         if it % args.eval_every == 0 or it == args.iters:
             evl.reset()

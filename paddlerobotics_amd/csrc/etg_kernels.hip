@@ -21,6 +21,7 @@
 #include "etg_core16.h"
 #include "policy_core.h"
 #include "../../include/etgsim_step_policy.h"
+#include "../../include/etgsim_collect.h"
 #include "../../include/etgsim_terminal.h"
 
 // ---- translation units.  The device code of this file is ~120 instantiations of the physics tick: four minutes of
@@ -1755,13 +1756,20 @@ struct StepPolOut {
   uint8_t* done;              // [N]
   float* info;                // [N,64], or NULL
 };
-template <bool FLAT, bool KNEE, bool PLAIN, bool AUTO>
+// the episode records of k_collect_policy16 (all NULL in the one-step kernels): the robot's running return and 1-based episode
+// step after the step and before a restart, and the bootstrap flag of the transition (replay.bootstrap_mask)
+struct EpOut { float* ret; int32_t* len; float* terminal; int bootstrap_from; };
+// LOOP (k_collect_policy16 calls the body once per control step): the lane and block indices go through an empty asm, so what the
+// body derives from them is formed anew in every iteration instead of being hoisted and kept in registers through the ticks
+template <bool FLAT, bool KNEE, bool PLAIN, bool AUTO, bool LOOP = false>
 __device__ __forceinline__ void step_policy16_body(const KCfg& K, const DevState& D, const PolicyW& P, float act_scale, float* obs,
                                                    const StepPolOut& O, const NextDyn& NX, float* lds_par, float* obs4, float* abuf,
-                                                   float* hA, float* hB, float* part, float (*act4)[16]) {
+                                                   float* hA, float* hB, float* part, float (*act4)[16],
+                                                   const EpOut E = EpOut{nullptr, nullptr, nullptr, 0}) {
   using namespace pol;
-  const int lane = threadIdx.x;
-  const int blk = xcd_contiguous_block();             // 4 robots; the host guarantees N % 16 == 0 (the grid is N / 4 exactly)
+  int lane = threadIdx.x;
+  int blk = xcd_contiguous_block();                   // 4 robots; the host guarantees N % 16 == 0 (the grid is N / 4 exactly)
+  if (LOOP) asm volatile("" : "+v"(lane), "+s"(blk));
   const size_t row0 = (size_t)blk * 4;
   // the actor: its rows, zero padded to WS columns, and (optionally) a copy of the rows for the replay memory
   WaveRing ring;
@@ -1815,6 +1823,12 @@ __device__ __forceinline__ void step_policy16_body(const KCfg& K, const DevState
   float r, d;
   control_step16_core(c, K, tp, L, S, D.ring, D.etgp, act, dflag, obs4, r, d, O.info ? O.info + row0 * ETG_INFO_DIM : (float*)nullptr);
   store_ctl16(c, K, S, D.ctl, D.ictl, D.legctl);
+  if (E.ret && c.r == 0) {
+    const int len = (int)S.len;
+    E.ret[c.env] = S.ret;
+    E.len[c.env] = len;
+    E.terminal[c.env] = (len >= E.bootstrap_from || d <= 0.5f) ? 1.0f : 0.0f;
+  }
   __syncthreads();
   for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) O.term_obs[row0 * ETG_OBS_DIM + idx] = obs4[idx];
   if (AUTO) {
@@ -1846,6 +1860,43 @@ template <bool FLAT, bool KNEE, bool PLAIN>
 __global__ void __launch_bounds__(BLOCK) k_step_policy16_ar(KCfg K, DevState D, PolicyW P, float act_scale, float* obs, StepPolOut O, NextDyn NX) {
   ETG_STEP_POLICY16_LDS
   step_policy16_body<FLAT, KNEE, PLAIN, true>(K, D, P, act_scale, obs, O, NX, lds_par, obs4, abuf, hA, hB, part, act4);
+}
+
+// ---- etg_collect_policy (include/etgsim_collect.h): n_steps closed-loop control steps WITH restarts in one launch.  A wave
+// stays with its 4 robots for the whole launch and never waits for another wave, so a robot that kneels for a few steps costs
+// its own wave's time only.  Every iteration is step_policy16_body<AUTO> on the step's slices of the [n_steps][N][...] records,
+// and the state is carried from one iteration to the next exactly as a launch boundary carries it: the body ends with
+// store_ctl16 / restart16 / store_state16 and the rows of obs4 in `obs`, and begins with load_state16 / load_ctl16 and the rows
+// of `obs` (L2-resident round trips of the wave's own lines, next to 13 physics ticks).  So one launch of K steps leaves bit for
+// bit what K launches of one step leave.  A restart finds no prepared next-episode dynamics (the host refuses such a handle:
+// a second restart inside the launch would find none), hence the null NextDyn.
+struct CollectOut {
+  const float* noise;         // [K,N,12] N(0,1) draws, or NULL (predict)
+  const float4* w3s;          // the packed log-std head and its bias: read when noise != NULL
+  const float* b3s;
+  const uint8_t* donef;       // [K,N] forced episode ends, or NULL
+  float *obs, *act, *rew;     // [K,N,49] the rows acted on, [K,N,12] unscaled actions, [K,N]
+  uint8_t* done;              // [K,N]
+  float *next_obs, *terminal, *ep_ret;   // [K,N,49] the step's rows before any restart, [K,N], [K,N]
+  int32_t* ep_len;            // [K,N]
+  float* info;                // [K,N,64], or NULL (etg_collect_policy passes NULL).  A run-time value on purpose: with a constant NULL
+                              // the reward terms lose their second use, the compiler contracts them into the reward's sum, and the
+                              // rewards stop being bit-equal to k_step_policy16_ar's (collect_continuous: chunked == per step)
+};
+template <bool FLAT, bool KNEE, bool PLAIN>
+__global__ void __launch_bounds__(BLOCK) k_collect_policy16(KCfg K, DevState D, PolicyW P, float act_scale, float* obs, CollectOut R,
+                                                             int n_steps, int bootstrap_from) {
+  ETG_STEP_POLICY16_LDS
+  const size_t N = K.n_env;
+  for (int s = 0; s < n_steps; s++) {
+    const size_t at = (size_t)s * N;
+    const StepPolOut O = {R.noise ? R.noise + at * ETG_ACT_DIM : nullptr, R.w3s, R.b3s, R.donef ? R.donef + at : nullptr,
+                          R.act + at * ETG_ACT_DIM, R.obs + at * ETG_OBS_DIM, R.next_obs + at * ETG_OBS_DIM, R.rew + at, R.done + at,
+                          R.info ? R.info + at * ETG_INFO_DIM : nullptr};
+    step_policy16_body<FLAT, KNEE, PLAIN, true, true>(K, D, P, act_scale, obs, O, NextDyn{nullptr, nullptr, nullptr}, lds_par, obs4, abuf, hA, hB,
+                                                      part, act4, EpOut{R.ep_ret + at, R.ep_len + at, R.terminal + at, bootstrap_from});
+    __syncthreads();                                  // the rows of obs4 are out before the next iteration stages them again
+  }
 }
 #undef ETG_STEP_POLICY16_LDS
 
@@ -2178,6 +2229,7 @@ __global__ void __launch_bounds__(256) k_term_ctx(KCfg K, DevState D, const uint
 #define ETG_ARGS_POLICY_REC KCfg, DevState, PolicyW, int, float, float*, RecOut
 #define ETG_ARGS_STEP_POLICY KCfg, DevState, PolicyW, float, float*, StepPolOut
 #define ETG_ARGS_STEP_POLICY_AR KCfg, DevState, PolicyW, float, float*, StepPolOut, NextDyn
+#define ETG_ARGS_COLLECT KCfg, DevState, PolicyW, float, float*, CollectOut, int, int
 #if ETG_TU_PARTS > 1
 #define ETG_SLOT_OWNER(S) (1 + ((S) - 1) % (ETG_TU_PARTS - 1))
 #if ETG_SLOT_OWNER(1) == ETG_TU_PART
@@ -2259,6 +2311,7 @@ ETG_INST16(k_rollout_policy16w, 2, 4, 6, 1, 3, 5, ETG_ARGS_POLICY)
 ETG_INST16(k_rollout_policy16w_rec, 7, 2, 4, 6, 1, 3, ETG_ARGS_POLICY_REC)
 ETG_INST16(k_step_policy16, 3, 5, 7, 2, 4, 6, ETG_ARGS_STEP_POLICY)
 ETG_INST16(k_step_policy16_ar, 6, 1, 3, 5, 7, 2, ETG_ARGS_STEP_POLICY_AR)
+ETG_INST16(k_collect_policy16, 4, 6, 1, 3, 5, 7, ETG_ARGS_COLLECT)
 ETG_INSTP16(k_rollout_policy16, false, 2, 3, 4, 5, 6, 7, ETG_ARGS_POLICY)
 ETG_INSTP16(k_rollout_policy16, true, 1, 2, 3, 4, 5, 6, ETG_ARGS_POLICY)
 ETG_INSTP16(k_rollout_policy16_rec, false, 7, 1, 2, 3, 4, 5, ETG_ARGS_POLICY_REC)
@@ -3076,6 +3129,43 @@ extern "C" int etg_step_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, in
       if (int rc = etg_clear_pushes(h, done, stream)) return rc;
     return etg_reset(h, done, obs, stream);
   }
+  return ETG_OK;
+}
+
+// n_steps closed-loop control steps with restarts in one launch (include/etgsim_collect.h): k_collect_policy16.  Every refusal
+// comes before any launch and before any change to the handle.
+extern "C" int etg_collect_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int n_steps,
+                                  int bootstrap_from, const float* noise, const uint8_t* donef, float* obs, float* rec_obs,
+                                  float* rec_action, float* rec_reward, uint8_t* rec_done, float* rec_next_obs, float* rec_terminal,
+                                  float* rec_ep_ret, int32_t* rec_ep_len, void* stream) {
+  CHECK_HANDLE(h);
+  if (!pol || !obs || !rec_obs || !rec_action || !rec_reward || !rec_done || !rec_next_obs || !rec_terminal || !rec_ep_ret || !rec_ep_len)
+    return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: policy, obs and the eight record arrays must be non-null");
+  if (n_steps < 1) return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: n_steps must be at least 1");
+  if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_collect_policy: call etg_reset first");
+  if (noise && !pol->has_std) return fail(ETG_ERR_STATE, "etg_collect_policy: sampling needs etg_policy_load_std() first");
+  if (int rc = policy_checks("etg_collect_policy", h, pol, obs_col0)) return rc;
+  if (precision != 0 || pol->in_dim > 4 * pol::KQ1)
+    return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: the kernel runs the fp32 per-wave actor tile: precision 0, in_dim <= 64");
+  if (h->lanes != 16 || h->N % 16 != 0)
+    return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: needs the 16-lanes-per-robot mapping and num_envs % 16 == 0");
+  if (h->K.motor_mode == 2) return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: the HYBRID motor mode is not covered (its action has 60 columns)");
+  if (h->K.noise_on) return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: sensor noise is not covered: switch it off or step");
+  if (h->NX.ok)
+    return fail(ETG_ERR_STATE, "etg_collect_policy: the handle has prepared next-episode dynamics (etg_prepare_next_dynamics): a second "
+                               "restart inside the launch would find no prepared row -- use etg_step_policy");
+  refresh_all_cached(h);
+  if (!h->all_cached)
+    return fail(ETG_ERR_STATE, "etg_collect_policy: no cached settle for every robot (a full etg_reset, or masked resets that covered "
+                               "every robot whose parameters, terrain or start offset changed) -- use etg_step_policy");
+  advance_obs_stream(h, 2 * n_steps);   // as n_steps etg_step_policy calls with a fused restart
+  const PolicyW Pq = policy_wave(pol, obs_col0);
+  const CollectOut R = {noise, (const float4*)pol->w3sq, pol->b3s, donef, rec_obs, rec_action, rec_reward, rec_done,
+                        rec_next_obs, rec_terminal, rec_ep_ret, rec_ep_len, nullptr};
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g(h->N / 4);
+  LAUNCH16(k_collect_policy16, g, s, h->K, h->D, Pq, act_scale, obs, R, n_steps, bootstrap_from);
+  HIP_TRY(hipGetLastError());
   return ETG_OK;
 }
 

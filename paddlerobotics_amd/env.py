@@ -880,6 +880,69 @@ class BatchedQuadrupedEnv:
             self._refresh_next_dynamics()
         return (self._last_view, self.reward, self.done.view(torch.bool) if want_info else self.done, info, act)
 
+    def collect_policy(self, policy, n_steps, act_scale=0.3, mode="sample", noise=None, donef=None, generator=None):
+        """n_steps closed-loop control steps of every robot, restarts included, in ONE launch (include/etgsim_collect.h): per
+        step what step_policy does on an auto_reset env -- the actor on the current observation (mode "sample": noise
+        [K,N,12] ~ N(0,1), drawn from `generator` when not given; "predict": tanh(mean)), the step with action * act_scale,
+        the restart of a finished robot, whose reset observation the next step acts on.  A wave keeps its 4 robots for the
+        whole launch and waits for nobody, which a launch per step cannot offer.  donef [K,N] (bool / uint8): forced episode
+        ends per step.
+
+        Returns a dict of device tensors, step-major: obs [K,N,D] (the rows acted on), action [K,N,12] (UNSCALED), reward
+        [K,N], done [K,N] (bool), next_obs [K,N,D] (the step's rows before any restart), terminal [K,N] (the bootstrap flag:
+        1 - done, 1 from episode step replay.BOOTSTRAP_ALWAYS_FROM on), ep_ret [K,N] and ep_len [K,N] (int32: the robot's
+        episode return and 1-based episode step after the step, before a restart).  D is the env's column view, as in
+        step_policy.  The tensors are the env's buffers for this K (or views of them): the next call with the same K writes over
+        them.  env.obs, the view step() returns next and episode_stats() continue exactly as after K step_policy calls.
+
+        FusedKernelUnavailable: what step_policy refuses, an env without auto_reset or with random_dynamics (a second restart
+        inside the launch would find no prepared dynamics), or robots without a cached settle (e.g. a heightfield with start
+        jitter)."""
+        if mode not in ("predict", "sample"):
+            raise ValueError("mode must be 'predict' or 'sample'")
+        why = self._step_policy_refusal(policy, 0)
+        if why:
+            raise FusedKernelUnavailable("step_policy: " + why)
+        if not self.auto_reset:
+            raise FusedKernelUnavailable("collect_policy restarts finished robots: it needs an env made with auto_reset=True")
+        if self._rand_dyn:
+            raise FusedKernelUnavailable("collect_policy: random_dynamics is not covered (a second restart inside the launch would "
+                                         "find no prepared dynamics): use step_policy")
+        N, K = self.num_envs, int(n_steps)
+        if K < 1:
+            raise ValueError("n_steps must be at least 1")
+        if mode == "sample":
+            if noise is None:
+                noise = torch.randn(K, N, A.NUM_MOTORS, device=self.device, generator=generator)
+            noise = self._f32(noise, (K, N, A.NUM_MOTORS), "noise")
+        elif noise is not None:
+            raise ValueError("noise is for mode='sample'")
+        if donef is not None:
+            donef = torch.as_tensor(donef, device=self.device).to(torch.uint8).contiguous()
+            if tuple(donef.shape) != (K, N):
+                raise ValueError("donef must have shape [n_steps, N]")
+        bufs = getattr(self, "_cp_buf", None)
+        if bufs is None or bufs["reward"].shape[0] != K:
+            z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=self.device)
+            bufs = self._cp_buf = {"obs": z(K, N, A.OBS_DIM), "action": z(K, N, A.NUM_MOTORS), "reward": z(K, N),
+                                   "done": z(K, N, dtype=torch.uint8), "next_obs": z(K, N, A.OBS_DIM), "terminal": z(K, N),
+                                   "ep_ret": z(K, N), "ep_len": z(K, N, dtype=torch.int32)}
+        from .replay import BOOTSTRAP_ALWAYS_FROM
+        rc = self._lib.etg_collect_policy(self._h, policy._h, C.c_float(act_scale), 0, int(self._cols[0]), K, int(BOOTSTRAP_ALWAYS_FROM),
+                                          _ptr(noise), _ptr(donef), _ptr(self.obs), _ptr(bufs["obs"]), _ptr(bufs["action"]),
+                                          _ptr(bufs["reward"]), _ptr(bufs["done"]), _ptr(bufs["next_obs"]), _ptr(bufs["terminal"]),
+                                          _ptr(bufs["ep_ret"]), _ptr(bufs["ep_len"]), self._stream())
+        if rc == _lib.ETG_ERR_STATE:   # (the env-level checks above leave the cached settles)
+            raise FusedKernelUnavailable("collect_policy: " + self._lib.etg_last_error().decode())
+        _lib.check(rc)
+        self._keep_step = (noise, donef)
+        self._last_view = self._obs_view()
+        sel = (lambda o: o) if self._col_idx is None else (lambda o: o.index_select(2, self._col_idx))
+        out = dict(bufs)
+        out["obs"], out["next_obs"] = sel(bufs["obs"]), sel(bufs["next_obs"])
+        out["done"] = bufs["done"].view(torch.bool)
+        return out
+
     def set_rollout_mode(self, simulate_finished=False):
         """The fused rollouts (rollout_openloop / _policy / _policy_record / _actions) stop simulating a robot when its episode
         ends, as the reference's loops do (pretrain.py:137-153, train.py:226-247): its state stays the terminal state, its

@@ -10,7 +10,8 @@ One env here is thousands of robots, so one `step()` yields a BATCH of transitio
 robots whose episode is still running into a ring of transitions that lives in HBM next to the simulator -- no host copy,
 no host synchronisation (the write position is a device scalar; rows of finished robots go to a scratch slot).
 `collect_transitions` is the batched run_train_episode / run_EStrain_episode collection loop; `collect_continuous` is the
-continuous form of run_train_episode's collection on an auto_reset env (one env.step_policy launch per control step).
+continuous form of run_train_episode's collection on an auto_reset env (one env.step_policy launch per control step, or one
+env.collect_policy launch per `chunk` steps).
 
 On a HIP device the appends go through etg_replay_begin / etg_replay_end (csrc/etg_replay.hip: prefix sum over the alive
 bytes + scattered rows, three launches per control step, the info sums and the alive update folded in); the torch
@@ -302,7 +303,7 @@ def collect_transitions(env, rpm, max_step, policy=None, action_bound=0.3, mode=
 
 
 def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="sample", noise=None, generator=None, donef=None,
-                       fused=None):
+                       fused=None, chunk=None):
     """Continuous collection for SAC (run_train_episode, train.py:129-179, batched without episode boundaries): n_steps control
     steps of every robot of an auto_reset env, every step's N transitions appended to `rpm`:
 
@@ -322,7 +323,13 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
     `generator`), "predict", or "uniform" (U(-1,1) actions without a policy: the warm-up of train.py:140-142).  donef [n_steps, N]
     (bool / uint8, optional): forced episode ends per step, e.g. a time limit (train.py:145 `donef=(steps > max_step)`).
     Returns (ret [N], len [N]): return and length of the LAST episode of each robot that ended during the call (len 0: none of
-    its episodes ended)."""
+    its episodes ended).
+
+    chunk=K: ceil(n_steps / K) env.collect_policy launches of up to K control steps each (the last one may be shorter) instead
+    of one launch per step; each launch's rows are appended step-major, the same fields in the same order.  Inside a launch a
+    wave never waits for another wave's kneeling robot.  Where collect_policy does not cover the configuration (what step_policy
+    refuses, random_dynamics, robots without a cached settle) the chunk's steps go through the per-step path above; fused=True
+    makes that an error (FusedKernelUnavailable), and fused=False or mode="uniform" ignore `chunk`."""
     if not env.auto_reset:
         raise ValueError("collect_continuous needs an env made with auto_reset=True")
     if mode not in ("predict", "sample", "uniform"):
@@ -331,6 +338,8 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
         raise ValueError("mode %r needs a policy" % mode)
     if mode == "uniform" and fused:
         raise ValueError("mode 'uniform' has no policy to fuse: fused must be None or False")
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError("chunk must be None or at least 1")
     n, dev, T = env.num_envs, env.device, int(n_steps)
     adim = env.action_space.shape[0]
     if noise is not None:
@@ -343,6 +352,8 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
         donef = torch.as_tensor(donef, device=dev).to(torch.uint8).contiguous()
         if tuple(donef.shape) != (T, n):
             raise ValueError("donef must be [n_steps, num_envs]")
+    insist = fused is True
+    chunked = chunk is not None and fused is not False and mode != "uniform"
     if fused is None:
         fused = mode != "uniform" and env._step_policy_refusal(policy, 0) is None
 
@@ -363,20 +374,58 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
         _, reward, done, info = env.step(action * action_bound, donef=df, want_info=False, terminal_obs=True)
         return obs, action, reward, done, info["terminal_obs"].reshape(n, -1)
 
-    run_ret, run_len = env.episode_stats()        # the episodes running now: this call continues them
     last_ret = torch.zeros(n, device=dev)
     last_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    for k in range(T):
-        obs, action, reward, done, next_obs = step(k)
-        d = done.view(-1).to(torch.bool)
-        run_ret = run_ret + reward
-        run_len = run_len + 1                       # the 1-based episode step of this transition, per robot
-        terminal = torch.where(run_len >= BOOTSTRAP_ALWAYS_FROM, torch.ones_like(reward), 1.0 - d.to(torch.float32))
-        rpm.append_batch(obs, action, reward, next_obs, terminal)
-        last_ret = torch.where(d, run_ret, last_ret)
-        last_len = torch.where(d, run_len, last_len)
-        run_ret = torch.where(d, torch.zeros_like(run_ret), run_ret)
-        run_len = torch.where(d, torch.zeros_like(run_len), run_len)
+
+    def per_step(k0, m):
+        """control steps k0 .. k0 + m - 1, one launch (or predict / sample + step) each"""
+        nonlocal last_ret, last_len
+        run_ret, run_len = env.episode_stats()        # the episodes running now: these steps continue them
+        for k in range(k0, k0 + m):
+            obs, action, reward, done, next_obs = step(k)
+            d = done.view(-1).to(torch.bool)
+            run_ret = run_ret + reward
+            run_len = run_len + 1                       # the 1-based episode step of this transition, per robot
+            terminal = torch.where(run_len >= BOOTSTRAP_ALWAYS_FROM, torch.ones_like(reward), 1.0 - d.to(torch.float32))
+            rpm.append_batch(obs, action, reward, next_obs, terminal)
+            last_ret = torch.where(d, run_ret, last_ret)
+            last_len = torch.where(d, run_len, last_len)
+            run_ret = torch.where(d, torch.zeros_like(run_ret), run_ret)
+            run_len = torch.where(d, torch.zeros_like(run_len), run_len)
+
+    def launch(k0, m):
+        """control steps k0 .. k0 + m - 1 in ONE env.collect_policy launch, their rows into rpm step-major; False: the
+        configuration is outside the kernel (nothing was changed)"""
+        from .env import FusedKernelUnavailable
+        nonlocal last_ret, last_len
+        try:
+            rec = env.collect_policy(policy, m, action_bound, mode, noise=None if noise is None else noise[k0:k0 + m],
+                                     donef=None if donef is None else donef[k0:k0 + m], generator=generator)
+        except FusedKernelUnavailable:
+            if insist:
+                raise
+            return False
+        per = max(1, rpm.max_size // n)               # steps per append: a batch must fit the ring (as store_recorded)
+        for t0 in range(0, m, per):
+            t1 = min(m, t0 + per)
+            rows = (t1 - t0) * n
+            rpm.append_batch(rec["obs"][t0:t1].reshape(rows, -1), rec["action"][t0:t1].reshape(rows, -1), rec["reward"][t0:t1].reshape(-1),
+                             rec["next_obs"][t0:t1].reshape(rows, -1), rec["terminal"][t0:t1].reshape(-1))
+        # the last episode of each robot that ended in this launch: ep_ret / ep_len of its last `done` step
+        idx = torch.arange(1, m + 1, device=dev).view(m, 1)
+        at = torch.where(rec["done"], idx, torch.zeros_like(idx)).amax(dim=0)      # 1 + the last done step; 0: none
+        pick = (at - 1).clamp(min=0).view(1, n)
+        last_ret = torch.where(at > 0, rec["ep_ret"].gather(0, pick).view(-1), last_ret)
+        last_len = torch.where(at > 0, rec["ep_len"].gather(0, pick).view(-1), last_len)
+        return True
+
+    if not chunked:
+        per_step(0, T)
+    else:
+        for k0 in range(0, T, int(chunk)):
+            m = min(int(chunk), T - k0)
+            if not launch(k0, m):
+                per_step(k0, m)
     return last_ret, last_len
 
 
