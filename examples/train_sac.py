@@ -5,12 +5,16 @@ robot with the stochastic actor (collect_continuous on an auto_reset env) altern
 actor the simulator uses being the one the learner has just updated (learner.policy).
 
 Usage: python examples/train_sac.py [--num-envs 4096] [--iters 200] [--collect-steps 1] [--collect-chunk 0] [--utd 4]
-                                    [--eval-every 50] [--out sac.pt] [--checkpoint DIR [--resume]]
+                                    [--eval-every 50] [--out sac.pt] [--checkpoint DIR [--resume]] [--log-episodes]
 --collect-chunk K: the --collect-steps control steps of an iteration run K to a launch (env.collect_policy) instead of one
 launch per step; 0 (the default) is the per-step path.
 --utd: updates per control step (the reference does one update of 256 rows per transition of its single robot).
 --checkpoint DIR: at every evaluation the whole run is written to DIR -- learner.pt (weights and optimizer state), memory.npz (the
-replay memory) and env.pt (env.state_dict(): every robot mid-episode) -- and --resume picks the run up from there."""
+replay memory) and env.pt (env.state_dict(): every robot mid-episode) -- and --resume picks the run up from there.
+--log-episodes: a monitor.EpisodeMonitor, attached right after env.reset(), is fed by every collection step; each evaluation line
+is followed by the reference's per-episode log values (train.py:363-366: episode_reward, episode_step, episode_{term},
+mean_{term}, success_rate) averaged over the training episodes that finished since the previous one.  With --checkpoint the
+monitor is saved (monitor.pt) and resumed too."""
 import argparse
 import os
 import sys
@@ -20,6 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from paddlerobotics_amd.env import make_env  # noqa: E402
+from paddlerobotics_amd.monitor import EpisodeMonitor  # noqa: E402
 from paddlerobotics_amd.replay import DeviceReplayMemory, collect_continuous  # noqa: E402
 from paddlerobotics_amd.sac import DeviceSAC  # noqa: E402
 
@@ -34,12 +39,14 @@ def _cpu(x):
     return x
 
 
-def save_checkpoint(path, it, learner, rpm, env):
+def save_checkpoint(path, it, learner, rpm, env, monitor=None, logged=0):
     os.makedirs(path, exist_ok=True)
     torch.save({"iter": it, "model": _cpu(dict(learner.state_dict())), "optimizer": _cpu(learner.optimizer_state())},
                os.path.join(path, "learner.pt"))
     rpm.save(os.path.join(path, "memory.npz"))
     torch.save(env.state_dict(), os.path.join(path, "env.pt"))
+    if monitor is not None:
+        torch.save({"monitor": monitor.state_dict(), "logged": logged}, os.path.join(path, "monitor.pt"))
 
 
 def main():
@@ -58,6 +65,7 @@ def main():
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--checkpoint", type=str, default=None)      # directory of the run's checkpoint (off by default)
     ap.add_argument("--resume", action="store_true")
+    ap.add_argument("--log-episodes", action="store_true")      # per-episode reward terms and success rate of the training episodes
     args = ap.parse_args()
     if args.resume and not args.checkpoint:
         ap.error("--resume needs --checkpoint DIR")
@@ -66,7 +74,8 @@ def main():
     obs_dim, act_dim = env.observation_space.shape[0], env.action_space.shape[0]
     learner = DeviceSAC(obs_dim, act_dim, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, device=args.device)
     rpm = DeviceReplayMemory(args.memory_size, obs_dim, act_dim, device=args.device)
-    first = 1
+    monitor = EpisodeMonitor(args.num_envs, device=args.device) if args.log_episodes else None
+    first, logged = 1, 0                                        # logged: the episodes the previous evaluation line has covered
     if args.resume:
         ck = torch.load(os.path.join(args.checkpoint, "learner.pt"), map_location="cpu")
         learner.load_state_dict(ck["model"])
@@ -74,15 +83,19 @@ def main():
         rpm.load(os.path.join(args.checkpoint, "memory.npz"))
         env.load_state_dict(torch.load(os.path.join(args.checkpoint, "env.pt"), map_location="cpu"))
         first = int(ck["iter"]) + 1
+        if monitor is not None and os.path.exists(os.path.join(args.checkpoint, "monitor.pt")):
+            mk = torch.load(os.path.join(args.checkpoint, "monitor.pt"), map_location="cpu")
+            monitor.load_state_dict(mk["monitor"])
+            logged = int(mk["logged"])
         print("resumed from %s at iteration %d, memory %d" % (args.checkpoint, first, rpm.size()))
     else:
         env.reset()
-        collect_continuous(env, rpm, args.warmup_steps, policy=learner.policy, action_bound=0.3, mode="uniform")
+        collect_continuous(env, rpm, args.warmup_steps, policy=learner.policy, action_bound=0.3, mode="uniform", monitor=monitor)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(first, args.iters + 1):
         collect_continuous(env, rpm, args.collect_steps, policy=learner.policy, action_bound=0.3, mode="sample",
-                           chunk=args.collect_chunk if args.collect_chunk > 0 else None)
+                           chunk=args.collect_chunk if args.collect_chunk > 0 else None, monitor=monitor)
         losses = learner.learn_from(rpm, args.batch_size, n_updates=args.utd * args.collect_steps)
         if it % args.eval_every == 0 or it == args.iters:
             evl.reset()
@@ -91,9 +104,14 @@ def main():
             print("iter %d: %.0f control steps/s, %.0f updates/s, memory %d, critic loss %.4f, actor loss %.4f, eval return %.3f"
                   % (it, (it - first + 1) * args.collect_steps / dt, (it - first + 1) * args.collect_steps * args.utd / dt, rpm.size(),
                      losses[-1, 0].item(), losses[-1, 1].item(), ret.mean().item()))
+            if monitor is not None:
+                log = monitor.summary(since=logged)
+                logged = int(monitor.count.item())
+                print("  train episodes %d (of %d): " % (log["episodes"], logged)
+                      + ", ".join("%s %.4g" % (k, v) for k, v in log.items() if k != "episodes"))
             learner.save(args.out)                      # the reference's checkpoint format: loads into its MujocoModel
             if args.checkpoint:
-                save_checkpoint(args.checkpoint, it, learner, rpm, env)
+                save_checkpoint(args.checkpoint, it, learner, rpm, env, monitor, logged)
     env.close()
     evl.close()
 

@@ -22,6 +22,7 @@
 #include "policy_core.h"
 #include "../../include/etgsim_step_policy.h"
 #include "../../include/etgsim_collect.h"
+#include "../../include/etgsim_monitor.h"
 #include "../../include/etgsim_terminal.h"
 
 // ---- translation units.  The device code of this file is ~120 instantiations of the physics tick: four minutes of
@@ -3133,40 +3134,62 @@ extern "C" int etg_step_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, in
 }
 
 // n_steps closed-loop control steps with restarts in one launch (include/etgsim_collect.h): k_collect_policy16.  Every refusal
-// comes before any launch and before any change to the handle.
-extern "C" int etg_collect_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int n_steps,
-                                  int bootstrap_from, const float* noise, const uint8_t* donef, float* obs, float* rec_obs,
-                                  float* rec_action, float* rec_reward, uint8_t* rec_done, float* rec_next_obs, float* rec_terminal,
-                                  float* rec_ep_ret, int32_t* rec_ep_len, void* stream) {
+// comes before any launch and before any change to the handle.  etg_collect_policy records no info rows (rec_info = NULL);
+// etg_collect_policy_info (include/etgsim_monitor.h) is the same launch with CollectOut::info set.
+static int collect_policy_launch(const char* fn_, EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int n_steps,
+                                 int bootstrap_from, const float* noise, const uint8_t* donef, float* obs, float* rec_obs,
+                                 float* rec_action, float* rec_reward, uint8_t* rec_done, float* rec_next_obs, float* rec_terminal,
+                                 float* rec_ep_ret, int32_t* rec_ep_len, float* rec_info, void* stream) {
+  const std::string fn(fn_);
   CHECK_HANDLE(h);
   if (!pol || !obs || !rec_obs || !rec_action || !rec_reward || !rec_done || !rec_next_obs || !rec_terminal || !rec_ep_ret || !rec_ep_len)
-    return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: policy, obs and the eight record arrays must be non-null");
-  if (n_steps < 1) return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: n_steps must be at least 1");
-  if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_collect_policy: call etg_reset first");
-  if (noise && !pol->has_std) return fail(ETG_ERR_STATE, "etg_collect_policy: sampling needs etg_policy_load_std() first");
-  if (int rc = policy_checks("etg_collect_policy", h, pol, obs_col0)) return rc;
+    return fail(ETG_ERR_BAD_ARG, fn + ": policy, obs and the eight record arrays must be non-null");
+  if (n_steps < 1) return fail(ETG_ERR_BAD_ARG, fn + ": n_steps must be at least 1");
+  if (!h->was_reset) return fail(ETG_ERR_STATE, fn + ": call etg_reset first");
+  if (noise && !pol->has_std) return fail(ETG_ERR_STATE, fn + ": sampling needs etg_policy_load_std() first");
+  if (int rc = policy_checks(fn_, h, pol, obs_col0)) return rc;
   if (precision != 0 || pol->in_dim > 4 * pol::KQ1)
-    return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: the kernel runs the fp32 per-wave actor tile: precision 0, in_dim <= 64");
+    return fail(ETG_ERR_BAD_ARG, fn + ": the kernel runs the fp32 per-wave actor tile: precision 0, in_dim <= 64");
   if (h->lanes != 16 || h->N % 16 != 0)
-    return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: needs the 16-lanes-per-robot mapping and num_envs % 16 == 0");
-  if (h->K.motor_mode == 2) return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: the HYBRID motor mode is not covered (its action has 60 columns)");
-  if (h->K.noise_on) return fail(ETG_ERR_BAD_ARG, "etg_collect_policy: sensor noise is not covered: switch it off or step");
+    return fail(ETG_ERR_BAD_ARG, fn + ": needs the 16-lanes-per-robot mapping and num_envs % 16 == 0");
+  if (h->K.motor_mode == 2) return fail(ETG_ERR_BAD_ARG, fn + ": the HYBRID motor mode is not covered (its action has 60 columns)");
+  if (h->K.noise_on) return fail(ETG_ERR_BAD_ARG, fn + ": sensor noise is not covered: switch it off or step");
   if (h->NX.ok)
-    return fail(ETG_ERR_STATE, "etg_collect_policy: the handle has prepared next-episode dynamics (etg_prepare_next_dynamics): a second "
+    return fail(ETG_ERR_STATE, fn + ": the handle has prepared next-episode dynamics (etg_prepare_next_dynamics): a second "
                                "restart inside the launch would find no prepared row -- use etg_step_policy");
   refresh_all_cached(h);
   if (!h->all_cached)
-    return fail(ETG_ERR_STATE, "etg_collect_policy: no cached settle for every robot (a full etg_reset, or masked resets that covered "
+    return fail(ETG_ERR_STATE, fn + ": no cached settle for every robot (a full etg_reset, or masked resets that covered "
                                "every robot whose parameters, terrain or start offset changed) -- use etg_step_policy");
   advance_obs_stream(h, 2 * n_steps);   // as n_steps etg_step_policy calls with a fused restart
   const PolicyW Pq = policy_wave(pol, obs_col0);
   const CollectOut R = {noise, (const float4*)pol->w3sq, pol->b3s, donef, rec_obs, rec_action, rec_reward, rec_done,
-                        rec_next_obs, rec_terminal, rec_ep_ret, rec_ep_len, nullptr};
+                        rec_next_obs, rec_terminal, rec_ep_ret, rec_ep_len, rec_info};
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(h->N / 4);
   LAUNCH16(k_collect_policy16, g, s, h->K, h->D, Pq, act_scale, obs, R, n_steps, bootstrap_from);
   HIP_TRY(hipGetLastError());
   return ETG_OK;
+}
+
+extern "C" int etg_collect_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int n_steps,
+                                  int bootstrap_from, const float* noise, const uint8_t* donef, float* obs, float* rec_obs,
+                                  float* rec_action, float* rec_reward, uint8_t* rec_done, float* rec_next_obs, float* rec_terminal,
+                                  float* rec_ep_ret, int32_t* rec_ep_len, void* stream) {
+  return collect_policy_launch("etg_collect_policy", h, pol, act_scale, precision, obs_col0, n_steps, bootstrap_from, noise, donef, obs,
+                               rec_obs, rec_action, rec_reward, rec_done, rec_next_obs, rec_terminal, rec_ep_ret, rec_ep_len, nullptr,
+                               stream);
+}
+
+// the same launch with the step's 64-column info rows recorded too (include/etgsim_monitor.h)
+extern "C" int etg_collect_policy_info(EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int n_steps,
+                                       int bootstrap_from, const float* noise, const uint8_t* donef, float* obs, float* rec_obs,
+                                       float* rec_action, float* rec_reward, uint8_t* rec_done, float* rec_next_obs,
+                                       float* rec_terminal, float* rec_ep_ret, int32_t* rec_ep_len, float* rec_info, void* stream) {
+  if (h && !rec_info) return fail(ETG_ERR_BAD_ARG, "etg_collect_policy_info: rec_info must be non-null");
+  return collect_policy_launch("etg_collect_policy_info", h, pol, act_scale, precision, obs_col0, n_steps, bootstrap_from, noise, donef,
+                               obs, rec_obs, rec_action, rec_reward, rec_done, rec_next_obs, rec_terminal, rec_ep_ret, rec_ep_len, rec_info,
+                               stream);
 }
 
 extern "C" int etg_leg_kinematics(EtgHandle* h, const float* q, int n, float* foot, float* jac, void* stream) {

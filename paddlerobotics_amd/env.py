@@ -880,7 +880,7 @@ class BatchedQuadrupedEnv:
             self._refresh_next_dynamics()
         return (self._last_view, self.reward, self.done.view(torch.bool) if want_info else self.done, info, act)
 
-    def collect_policy(self, policy, n_steps, act_scale=0.3, mode="sample", noise=None, donef=None, generator=None):
+    def collect_policy(self, policy, n_steps, act_scale=0.3, mode="sample", noise=None, donef=None, generator=None, want_info=False):
         """n_steps closed-loop control steps of every robot, restarts included, in ONE launch (include/etgsim_collect.h): per
         step what step_policy does on an auto_reset env -- the actor on the current observation (mode "sample": noise
         [K,N,12] ~ N(0,1), drawn from `generator` when not given; "predict": tanh(mean)), the step with action * act_scale,
@@ -894,6 +894,11 @@ class BatchedQuadrupedEnv:
         episode return and 1-based episode step after the step, before a restart).  D is the env's column view, as in
         step_policy.  The tensors are the env's buffers for this K (or views of them): the next call with the same K writes over
         them.  env.obs, the view step() returns next and episode_stats() continue exactly as after K step_policy calls.
+
+        want_info=True: the dict also has info [K,N,64], every step's info row (env.info_buf's layout; of a robot that restarts,
+        the finished step's row) -- what monitor.EpisodeMonitor.update_chunk reduces per episode.  The launch is the same
+        kernel through etg_collect_policy_info (include/etgsim_monitor.h); everything else the call returns or changes is the
+        same as without it.
 
         FusedKernelUnavailable: what step_policy refuses, an env without auto_reset or with random_dynamics (a second restart
         inside the launch would find no prepared dynamics), or robots without a cached settle (e.g. a heightfield with start
@@ -928,10 +933,16 @@ class BatchedQuadrupedEnv:
                                    "done": z(K, N, dtype=torch.uint8), "next_obs": z(K, N, A.OBS_DIM), "terminal": z(K, N),
                                    "ep_ret": z(K, N), "ep_len": z(K, N, dtype=torch.int32)}
         from .replay import BOOTSTRAP_ALWAYS_FROM
-        rc = self._lib.etg_collect_policy(self._h, policy._h, C.c_float(act_scale), 0, int(self._cols[0]), K, int(BOOTSTRAP_ALWAYS_FROM),
-                                          _ptr(noise), _ptr(donef), _ptr(self.obs), _ptr(bufs["obs"]), _ptr(bufs["action"]),
-                                          _ptr(bufs["reward"]), _ptr(bufs["done"]), _ptr(bufs["next_obs"]), _ptr(bufs["terminal"]),
-                                          _ptr(bufs["ep_ret"]), _ptr(bufs["ep_len"]), self._stream())
+        args = (self._h, policy._h, C.c_float(act_scale), 0, int(self._cols[0]), K, int(BOOTSTRAP_ALWAYS_FROM), _ptr(noise), _ptr(donef),
+                _ptr(self.obs), _ptr(bufs["obs"]), _ptr(bufs["action"]), _ptr(bufs["reward"]), _ptr(bufs["done"]), _ptr(bufs["next_obs"]),
+                _ptr(bufs["terminal"]), _ptr(bufs["ep_ret"]), _ptr(bufs["ep_len"]))
+        if want_info:
+            ibuf = getattr(self, "_cp_info", None)
+            if ibuf is None or ibuf.shape[0] != K:
+                ibuf = self._cp_info = torch.zeros(K, N, A.INFO_DIM, device=self.device)
+            rc = self._lib.etg_collect_policy_info(*args, _ptr(ibuf), self._stream())
+        else:
+            rc = self._lib.etg_collect_policy(*args, self._stream())
         if rc == _lib.ETG_ERR_STATE:   # (the env-level checks above leave the cached settles)
             raise FusedKernelUnavailable("collect_policy: " + self._lib.etg_last_error().decode())
         _lib.check(rc)
@@ -941,6 +952,8 @@ class BatchedQuadrupedEnv:
         out = dict(bufs)
         out["obs"], out["next_obs"] = sel(bufs["obs"]), sel(bufs["next_obs"])
         out["done"] = bufs["done"].view(torch.bool)
+        if want_info:
+            out["info"] = ibuf
         return out
 
     def set_rollout_mode(self, simulate_finished=False):

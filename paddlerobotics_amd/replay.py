@@ -303,7 +303,7 @@ def collect_transitions(env, rpm, max_step, policy=None, action_bound=0.3, mode=
 
 
 def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="sample", noise=None, generator=None, donef=None,
-                       fused=None, chunk=None):
+                       fused=None, chunk=None, monitor=None):
     """Continuous collection for SAC (run_train_episode, train.py:129-179, batched without episode boundaries): n_steps control
     steps of every robot of an auto_reset env, every step's N transitions appended to `rpm`:
 
@@ -329,7 +329,12 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
     of one launch per step; each launch's rows are appended step-major, the same fields in the same order.  Inside a launch a
     wave never waits for another wave's kneeling robot.  Where collect_policy does not cover the configuration (what step_policy
     refuses, random_dynamics, robots without a cached settle) the chunk's steps go through the per-step path above; fused=True
-    makes that an error (FusedKernelUnavailable), and fused=False or mode="uniform" ignore `chunk`."""
+    makes that an error (FusedKernelUnavailable), and fused=False or mode="uniform" ignore `chunk`.
+
+    monitor: a monitor.EpisodeMonitor that is fed every step's reward, done and info row (the per-episode reward terms and
+    success rate of train.py:150-157,175): update_chunk on a launch's records, update after a single step.  The steps then also
+    write their info rows (want_info=True); what is stored and returned is the same.  Without one the calls made are the same
+    as before the monitor existed."""
     if not env.auto_reset:
         raise ValueError("collect_continuous needs an env made with auto_reset=True")
     if mode not in ("predict", "sample", "uniform"):
@@ -362,7 +367,9 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
         df = None if donef is None else donef[k]
         if fused:
             _, reward, done, info, action = env.step_policy(policy, action_bound, mode, noise=None if noise is None else noise[k],
-                                                            donef=df, want_info=False, generator=generator)
+                                                            donef=df, want_info=monitor is not None, generator=generator)
+            if monitor is not None:
+                monitor.update(reward, done, env.info_buf)
             return info["acted_obs"], action, reward, done, info["terminal_obs"]
         obs = env._last_view.reshape(n, -1).clone()   # (the env's buffer, or a view of it: the step writes over it)
         if mode == "uniform":
@@ -371,7 +378,9 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
             action = policy.sample(obs, 1.0, noise=None if noise is None else noise[k], generator=generator, return_logp=False)
         else:
             action = policy.predict(obs, 1.0)
-        _, reward, done, info = env.step(action * action_bound, donef=df, want_info=False, terminal_obs=True)
+        _, reward, done, info = env.step(action * action_bound, donef=df, want_info=monitor is not None, terminal_obs=True)
+        if monitor is not None:
+            monitor.update(reward, done, env.info_buf)
         return obs, action, reward, done, info["terminal_obs"].reshape(n, -1)
 
     last_ret = torch.zeros(n, device=dev)
@@ -398,13 +407,16 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
         configuration is outside the kernel (nothing was changed)"""
         from .env import FusedKernelUnavailable
         nonlocal last_ret, last_len
+        kw = {} if monitor is None else {"want_info": True}
         try:
             rec = env.collect_policy(policy, m, action_bound, mode, noise=None if noise is None else noise[k0:k0 + m],
-                                     donef=None if donef is None else donef[k0:k0 + m], generator=generator)
+                                     donef=None if donef is None else donef[k0:k0 + m], generator=generator, **kw)
         except FusedKernelUnavailable:
             if insist:
                 raise
             return False
+        if monitor is not None:
+            monitor.update_chunk(rec["reward"], rec["done"], rec["info"])
         per = max(1, rpm.max_size // n)               # steps per append: a batch must fit the ring (as store_recorded)
         for t0 in range(0, m, per):
             t1 = min(m, t0 + per)
