@@ -5,7 +5,7 @@ robot with the stochastic actor (collect_continuous on an auto_reset env) altern
 actor the simulator uses being the one the learner has just updated (learner.policy).
 
 Usage: python examples/train_sac.py [--num-envs 4096] [--iters 200] [--collect-steps 1] [--collect-chunk 0] [--utd 4]
-                                    [--eval-every 50] [--out sac.pt] [--checkpoint DIR [--resume]] [--log-episodes]
+                                    [--eval-every 50] [--out sac.pt] [--checkpoint DIR [--resume]] [--log-episodes] [--n-step 1]
 --collect-chunk K: the --collect-steps control steps of an iteration run K to a launch (env.collect_policy) instead of one
 launch per step; 0 (the default) is the per-step path.
 --utd: updates per control step (the reference does one update of 256 rows per transition of its single robot).
@@ -14,7 +14,10 @@ replay memory) and env.pt (env.state_dict(): every robot mid-episode) -- and --r
 --log-episodes: a monitor.EpisodeMonitor, attached right after env.reset(), is fed by every collection step; each evaluation line
 is followed by the reference's per-episode log values (train.py:363-366: episode_reward, episode_step, episode_{term},
 mean_{term}, success_rate) averaged over the training episodes that finished since the previous one.  With --checkpoint the
-monitor is saved (monitor.pt) and resumed too."""
+monitor is saved (monitor.pt) and resumed too.
+--n-step N: the memory receives N-step rows (nstep.NStepWriter with the learner's gamma: the discounted sum of N rewards, the
+observation N steps later, terminal * gamma^(N-1)), so that one update carries reward N control steps back; 1 (the default)
+takes the 1-step path as it was.  With --checkpoint the writer is saved (nstep.pt) and resumed too."""
 import argparse
 import os
 import sys
@@ -25,6 +28,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from paddlerobotics_amd.env import make_env  # noqa: E402
 from paddlerobotics_amd.monitor import EpisodeMonitor  # noqa: E402
+from paddlerobotics_amd.nstep import NStepWriter  # noqa: E402
 from paddlerobotics_amd.replay import DeviceReplayMemory, collect_continuous  # noqa: E402
 from paddlerobotics_amd.sac import DeviceSAC  # noqa: E402
 
@@ -39,7 +43,7 @@ def _cpu(x):
     return x
 
 
-def save_checkpoint(path, it, learner, rpm, env, monitor=None, logged=0):
+def save_checkpoint(path, it, learner, rpm, env, monitor=None, logged=0, writer=None):
     os.makedirs(path, exist_ok=True)
     torch.save({"iter": it, "model": _cpu(dict(learner.state_dict())), "optimizer": _cpu(learner.optimizer_state())},
                os.path.join(path, "learner.pt"))
@@ -47,6 +51,8 @@ def save_checkpoint(path, it, learner, rpm, env, monitor=None, logged=0):
     torch.save(env.state_dict(), os.path.join(path, "env.pt"))
     if monitor is not None:
         torch.save({"monitor": monitor.state_dict(), "logged": logged}, os.path.join(path, "monitor.pt"))
+    if writer is not None:
+        torch.save(writer.state_dict(), os.path.join(path, "nstep.pt"))
 
 
 def main():
@@ -66,6 +72,7 @@ def main():
     ap.add_argument("--checkpoint", type=str, default=None)      # directory of the run's checkpoint (off by default)
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--log-episodes", action="store_true")      # per-episode reward terms and success rate of the training episodes
+    ap.add_argument("--n-step", type=int, default=1)            # rows of this many control steps (1: the 1-step path as it was)
     args = ap.parse_args()
     if args.resume and not args.checkpoint:
         ap.error("--resume needs --checkpoint DIR")
@@ -75,6 +82,7 @@ def main():
     learner = DeviceSAC(obs_dim, act_dim, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, device=args.device)
     rpm = DeviceReplayMemory(args.memory_size, obs_dim, act_dim, device=args.device)
     monitor = EpisodeMonitor(args.num_envs, device=args.device) if args.log_episodes else None
+    writer = NStepWriter(rpm, args.num_envs, args.n_step, learner.gamma) if args.n_step > 1 else None
     first, logged = 1, 0                                        # logged: the episodes the previous evaluation line has covered
     if args.resume:
         ck = torch.load(os.path.join(args.checkpoint, "learner.pt"), map_location="cpu")
@@ -87,15 +95,19 @@ def main():
             mk = torch.load(os.path.join(args.checkpoint, "monitor.pt"), map_location="cpu")
             monitor.load_state_dict(mk["monitor"])
             logged = int(mk["logged"])
+        if writer is not None:
+            writer.load_state_dict(torch.load(os.path.join(args.checkpoint, "nstep.pt"), map_location="cpu"))
         print("resumed from %s at iteration %d, memory %d" % (args.checkpoint, first, rpm.size()))
     else:
         env.reset()
-        collect_continuous(env, rpm, args.warmup_steps, policy=learner.policy, action_bound=0.3, mode="uniform", monitor=monitor)
+        # (with N-step rows the first row of a robot closes at its N-th step: warm up at least that long, so that the first update finds rows)
+        collect_continuous(env, rpm, max(args.warmup_steps, args.n_step), policy=learner.policy, action_bound=0.3, mode="uniform", monitor=monitor,
+                           nstep=writer)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(first, args.iters + 1):
         collect_continuous(env, rpm, args.collect_steps, policy=learner.policy, action_bound=0.3, mode="sample",
-                           chunk=args.collect_chunk if args.collect_chunk > 0 else None, monitor=monitor)
+                           chunk=args.collect_chunk if args.collect_chunk > 0 else None, monitor=monitor, nstep=writer)
         losses = learner.learn_from(rpm, args.batch_size, n_updates=args.utd * args.collect_steps)
         if it % args.eval_every == 0 or it == args.iters:
             evl.reset()
@@ -111,7 +123,7 @@ def main():
                       + ", ".join("%s %.4g" % (k, v) for k, v in log.items() if k != "episodes"))
             learner.save(args.out)                      # the reference's checkpoint format: loads into its MujocoModel
             if args.checkpoint:
-                save_checkpoint(args.checkpoint, it, learner, rpm, env, monitor, logged)
+                save_checkpoint(args.checkpoint, it, learner, rpm, env, monitor, logged, writer)
     env.close()
     evl.close()
 

@@ -303,7 +303,7 @@ def collect_transitions(env, rpm, max_step, policy=None, action_bound=0.3, mode=
 
 
 def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="sample", noise=None, generator=None, donef=None,
-                       fused=None, chunk=None, monitor=None):
+                       fused=None, chunk=None, monitor=None, nstep=None):
     """Continuous collection for SAC (run_train_episode, train.py:129-179, batched without episode boundaries): n_steps control
     steps of every robot of an auto_reset env, every step's N transitions appended to `rpm`:
 
@@ -334,7 +334,12 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
     monitor: a monitor.EpisodeMonitor that is fed every step's reward, done and info row (the per-episode reward terms and
     success rate of train.py:150-157,175): update_chunk on a launch's records, update after a single step.  The steps then also
     write their info rows (want_info=True); what is stored and returned is the same.  Without one the calls made are the same
-    as before the monitor existed."""
+    as before the monitor existed.
+
+    nstep: an nstep.NStepWriter on `rpm` (for the same number of robots): on each of the three paths the step's or the launch's
+    records -- the fields above with done and the robot's 1-based episode step -- go through the writer instead of
+    rpm.append_batch, and `rpm` receives n-step rows (nstep.py; the newest n - 1 steps stay pending in the writer until later
+    steps or its flush() close them).  The return value is the same.  Without one the calls made are the same as before."""
     if not env.auto_reset:
         raise ValueError("collect_continuous needs an env made with auto_reset=True")
     if mode not in ("predict", "sample", "uniform"):
@@ -345,6 +350,11 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
         raise ValueError("mode 'uniform' has no policy to fuse: fused must be None or False")
     if chunk is not None and int(chunk) < 1:
         raise ValueError("chunk must be None or at least 1")
+    if nstep is not None:
+        if getattr(nstep, "rpm", None) is not rpm:
+            raise ValueError("nstep must be an NStepWriter on the memory passed as rpm")
+        if nstep.num_envs != env.num_envs:
+            raise ValueError("nstep is for %d robots, the env has %d" % (nstep.num_envs, env.num_envs))
     n, dev, T = env.num_envs, env.device, int(n_steps)
     adim = env.action_space.shape[0]
     if noise is not None:
@@ -396,7 +406,10 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
             run_ret = run_ret + reward
             run_len = run_len + 1                       # the 1-based episode step of this transition, per robot
             terminal = torch.where(run_len >= BOOTSTRAP_ALWAYS_FROM, torch.ones_like(reward), 1.0 - d.to(torch.float32))
-            rpm.append_batch(obs, action, reward, next_obs, terminal)
+            if nstep is None:
+                rpm.append_batch(obs, action, reward, next_obs, terminal)
+            else:
+                nstep.append_step(obs, action, reward, d, next_obs, terminal, run_len)
             last_ret = torch.where(d, run_ret, last_ret)
             last_len = torch.where(d, run_len, last_len)
             run_ret = torch.where(d, torch.zeros_like(run_ret), run_ret)
@@ -417,8 +430,10 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
             return False
         if monitor is not None:
             monitor.update_chunk(rec["reward"], rec["done"], rec["info"])
+        if nstep is not None:
+            nstep.append_chunk(rec["obs"], rec["action"], rec["reward"], rec["done"], rec["next_obs"], rec["terminal"], rec["ep_len"])
         per = max(1, rpm.max_size // n)               # steps per append: a batch must fit the ring (as store_recorded)
-        for t0 in range(0, m, per):
+        for t0 in range(0, m if nstep is None else 0, per):
             t1 = min(m, t0 + per)
             rows = (t1 - t0) * n
             rpm.append_batch(rec["obs"][t0:t1].reshape(rows, -1), rec["action"][t0:t1].reshape(rows, -1), rec["reward"][t0:t1].reshape(-1),
