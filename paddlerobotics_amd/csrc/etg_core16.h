@@ -12,7 +12,8 @@
 // quad_perm scans, leg-level gathers are quad_perm broadcasts, robot-level reductions are 4-step
 // row butterflies (quad xor1, xor2, row_half_mirror, row_mirror), the sequential contact solve
 // broadcasts one row's impulse change with row_newbcast, and the Delassus row of a lane is 72
-// fused broadcast-FMAs (v_fmac_f32_dpp row_newbcast) against the row's Z vectors.
+// fused broadcast-FMAs (v_fmac_f32_dpp row_newbcast) against the row's Z vectors -- on the device 24 matrix
+// instructions with the A operand broadcast inside the row (gram16.h; kGramMfma below).
 // State lives in the same HBM arrays as the 4-lane kernel (etg_layout.h), so both kernels are
 // interchangeable on one handle.
 #pragma once
@@ -29,6 +30,12 @@ template <class Ctx, class = void> struct sweep_stream_ : std::false_type {};
 template <class Ctx> struct sweep_stream_<Ctx, std::void_t<decltype(Ctx::kSweepStream)>> : std::bool_constant<Ctx::kSweepStream> {};
 // (the call goes through a template of its own: contexts without the stream never instantiate it)
 template <class Ctx, class... Args> ETG_HD void run_sweep_stream_(const Ctx& c, Args&&... args) { c.pgs_body_stream(args...); }
+// Ctx::kGramMfma: the context builds four Gram columns of a row per matrix instruction (GpuCtx16::gram16, gram16.h):
+//     c[lp][e] = sum over k of a[k]@(lane 4 lp + e of the robot's row) * b[k],  lp, e = 0..3,
+// the same bits as 16 chains of fmac_rbcast.  The Delassus columns A / Ak and the second rows' BA are then built that way; a
+// context that does not say so (the emulation's, the CPU ABI's) runs the broadcast-FMA statements, which stay the definition.
+template <class Ctx, class = void> struct gram_mfma_ : std::false_type {};
+template <class Ctx> struct gram_mfma_<Ctx, std::void_t<decltype(Ctx::kGramMfma)>> : std::bool_constant<Ctx::kGramMfma> {};
 
 template <class F> struct State16 {
   V3<F> p;
@@ -393,25 +400,43 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
   c.phase(5);
   // ---- Delassus row of this lane: A[l'][e] = Z_own . Z_(l',e) over the 6 base coordinates, every term one
   // fused broadcast-FMA (v_fmac_f32_dpp row_newbcast); rows of the own leg add the leg compliance
-  // J_l H^-1 J_l^T.  (The 4-lane kernel contracts the same products on the matrix pipe; with one row per
-  // lane the DPP form needs no accumulator shuffles and no MFMA latency padding.)
+  // J_l H^-1 J_l^T.  (The 4-lane kernel contracts the same products on the matrix pipe; so does the device build
+  // of this mapping, with the A operand broadcast inside the row: see `gram` below.)
   // warm start (defined here: DPP source below): the normal row x K.warmstart, the friction rows x K.warmstart_t (Bullet's
   // multibody solver restarts friction rows from zero); the aux lane's body normal x K.warmstart_b (= warmstart when the body
   // contact is one persistent point, 0 otherwise: etg_layout.h), the body contact's friction rows start at 0
   F lam = rowf * sel_(s0, F(K.warmstart), sel_(c.sub_is(3), F(K.warmstart_b), F(K.warmstart_t))) * L.lam;
   F hj[3] = {HJ0, HJ1, HJ2};
-  c.dpp_ready10(Z, hj, &lam);                                   // one fence for all broadcast sources of this phase
+  // Where the context says kGramMfma, the four columns of leg lp -- A[lp][0..2] and the body normal row's Ak[lp] -- are ONE
+  // matrix instruction per base coordinate (v_mfma_f32_4x4x1 with the A operand broadcast from leg lp of the robot's row:
+  // gram16.h): one block of 24 instructions, k-major so that the four chains interleave, instead of 72 + 24 broadcast-FMAs.  Each
+  // output is the same fused multiply-add chain in the same order, seeded with -0 (fma(a, b, -0) = a b): the same bits.
+  constexpr bool gram = gram_mfma_<Ctx>::value;
   F A[4][3];
+  F Akz[4] = {zero, zero, zero, zero};                          // gram: Z_own . Z_(l', body normal), the fourth output (finish_tick: Ak)
+  if constexpr (gram) {
+    c.dpp_ready4(hj, &lam);                                     // (Z is no broadcast source on this path)
+    typename Ctx::gram_t Af[4];
+    c.gram16(Af, Z, Z);
 #pragma unroll
-  for (int lp = 0; lp < 4; lp++)
+    for (int lp = 0; lp < 4; lp++) {
 #pragma unroll
-    for (int e = 0; e < 3; e++) A[lp][e] = c.rbcast(Z[0], 4 * lp + e) * Z[0];
-#pragma unroll
-  for (int k = 1; k < 6; k++)
+      for (int e = 0; e < 3; e++) A[lp][e] = Af[lp][e];
+      Akz[lp] = Af[lp][3];
+    }
+  } else {
+    c.dpp_ready10(Z, hj, &lam);                                 // one fence for all broadcast sources of this phase
 #pragma unroll
     for (int lp = 0; lp < 4; lp++)
 #pragma unroll
-      for (int e = 0; e < 3; e++) c.fmac_rbcast(A[lp][e], Z[k], Z[k], 4 * lp + e);
+      for (int e = 0; e < 3; e++) A[lp][e] = c.rbcast(Z[0], 4 * lp + e) * Z[0];
+#pragma unroll
+    for (int k = 1; k < 6; k++)
+#pragma unroll
+      for (int lp = 0; lp < 4; lp++)
+#pragma unroll
+        for (int e = 0; e < 3; e++) c.fmac_rbcast(A[lp][e], Z[k], Z[k], 4 * lp + e);
+  }
   F ownl[4];
 #pragma unroll
   for (int lp = 0; lp < 4; lp++) ownl[lp] = sel_(c.leg_is(lp), one, zero);
@@ -491,9 +516,13 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
   if (body) {
 #pragma unroll
     for (int lp = 0; lp < 4; lp++) {
-      Ak[lp] = c.rbcast(Z[0], 4 * lp + 3) * Z[0];
+      if constexpr (gram) {
+        Ak[lp] = Akz[lp];                                         // made with A's columns in phase 5, at no instruction of its own
+      } else {
+        Ak[lp] = c.rbcast(Z[0], 4 * lp + 3) * Z[0];
 #pragma unroll
-      for (int k = 1; k < 6; k++) c.fmac_rbcast(Ak[lp], Z[k], Z[k], 4 * lp + 3);
+        for (int k = 1; k < 6; k++) c.fmac_rbcast(Ak[lp], Z[k], Z[k], 4 * lp + 3);
+      }
     }
     F ownk = c.qb(hj[0], 3) * Jl0;
     c.fmac_qb(ownk, hj[1], Jl1, 3);
@@ -566,13 +595,26 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
     u2s = rowf2 * dot(dir2, vc2);
     c.dpp_ready(Z2, 6);
     c.dpp_ready(hj2, 3);
+    // BA: four columns per matrix instruction, as A / Ak in phase 5 (96 broadcast-FMAs -> 24 instructions).  BB / AT use two of
+    // an instruction's four outputs, which at what a lone wave pays for the instruction between VALU work is no gain: they keep
+    // the broadcast-FMA form (tools/ubench/mfma4x4_bcast.hip, profiles/r09_ab_experiments.txt section 1).
+    if constexpr (gram) {
+      typename Ctx::gram_t Bf[4];
+      c.gram16(Bf, Z, Z2);
+#pragma unroll
+      for (int lp = 0; lp < 4; lp++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) BA[lp][e] = Bf[lp][e];
+    }
 #pragma unroll
     for (int lp = 0; lp < 4; lp++) {
 #pragma unroll
       for (int e = 0; e < 4; e++) {
-        BA[lp][e] = c.rbcast(Z[0], 4 * lp + e) * Z2[0];
+        if constexpr (!gram) {
+          BA[lp][e] = c.rbcast(Z[0], 4 * lp + e) * Z2[0];
 #pragma unroll
-        for (int k = 1; k < 6; k++) c.fmac_rbcast(BA[lp][e], Z[k], Z2[k], 4 * lp + e);
+          for (int k = 1; k < 6; k++) c.fmac_rbcast(BA[lp][e], Z[k], Z2[k], 4 * lp + e);
+        }
       }
 #pragma unroll
       for (int t = 0; t < 2; t++) {

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "etg_core16.h"
+#include "gram16.h"
 #include "policy_core.h"
 #include "../../include/etgsim_step_policy.h"
 #include "../../include/etgsim_collect.h"
@@ -698,6 +699,13 @@ struct GpuCtx16 {
     v = __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, v, 0, 0, 0);
     acc[0] = v[0]; acc[1] = v[1]; acc[2] = v[2]; acc[3] = v[3];
   }
+  // ---- four Gram columns per matrix instruction (gram16.h; etg_core16.h: kGramMfma): c[lp][e] = sum over the six base
+  // coordinates of a[k]@(lane 4 lp + e of the robot's row) * b[k] -- the 16 columns of a row set in one block of 24
+  // instructions, bit for bit what 16 chains of one product and five fmac_rbcast compute
+  typedef gram4_t gram_t;
+  __device__ __forceinline__ void gram16(gram_t (&c)[4], const float* a, const float* b) const { gram16_block(c, gram4_seed(), a, b); }
+  // the broadcast sources that remain DPP operands once the Z vectors go through the matrix pipe (dpp_ready10 without Z)
+  __device__ __forceinline__ void dpp_ready4(float* hj, float* lam) const { asm volatile("s_nop 1" : "+v"(hj[0]), "+v"(hj[1]), "+v"(hj[2]), "+v"(lam[0])); }
   // ---- fused broadcast-multiply-accumulate: acc += x@lane(r0 of the row / j of the quad) * y in ONE VOP2-DPP
   // instruction.  The compiler's DPP combiner only folds v_mov_dpp into mul/add (FMAs are still VOP3 when it
   // runs), so the FMA form is spelled out.  HAZARD: the hardware wants 2 wait states between the VALU write
@@ -1157,6 +1165,13 @@ template <bool FLAT, bool KNEE = false, bool PLAIN = false, bool SLOTB_LDS = fal
   static constexpr bool kAsmSweep = false;
 #else
   static constexpr bool kAsmSweep = true;     // pgs_normals / pgs_tangents_disc: the hand-scheduled sweep
+#endif
+  // the Delassus columns A / Ak and the body friction rows' BA come from the matrix pipe, four columns per instruction
+  // (gram16.h); -DETG_GRAM_DPP (A/B build variant): the broadcast-FMA form, which is also the C++ statement of the columns
+#ifdef ETG_GRAM_DPP
+  static constexpr bool kGramMfma = false;
+#else
+  static constexpr bool kGramMfma = true;
 #endif
   // -DETG_SWEEP_BOOKKEEPING_OUTSIDE (A/B build variant): the round-7 form, sweep_and_test's own statements around the asm blocks
 #if defined(ETG_NO_ASM_SWEEP) || defined(ETG_SWEEP_BOOKKEEPING_OUTSIDE) || defined(ETG_EAGER_FREEZE)
