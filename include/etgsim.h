@@ -268,7 +268,14 @@ int etg_set_motor_strength(EtgHandle* h, const float* ratios, const uint8_t* mas
  * absent, this one is the repo's): call once per control step before etg_step. A robot without an active push
  * starts one with probability `prob`: a horizontal force of magnitude U(fmin, fmax) N in a uniform direction,
  * held for `duration_steps` control steps, then removed. Counter-based RNG keyed by (seed, robot, call index),
- * so a run is reproducible. Robots being reset should have their push cleared with etg_clear_pushes.  */
+ * so a run is reproducible. Robots being reset should have their push cleared with etg_clear_pushes.
+ * The call that removes a robot's push draws nothing for it and starts none, so pushes of one robot are at least one
+ * control step apart. The call index counts the accepted calls: a refused one (ETG_ERR_BAD_ARG: prob < 0,
+ * duration_steps < 1, fmax < fmin) changes no force and leaves the stream where it was.
+ * The fused multi-step launches (etg_rollout_openloop / _actions / _policy / _policy_record, the collection launch of
+ * etgsim_collect.h) do not sample: they would hold an active push for all their steps and start none. The Python layer steps such an env
+ * (rollout_openloop, rollout_policy) or refuses (FusedKernelUnavailable).
+ * tests/push_ref.py states the schedule and the generator on the host.                                    */
 int etg_random_pushes(EtgHandle* h, uint64_t seed, float prob, int duration_steps, float fmin, float fmax,
                       void* stream);
 int etg_clear_pushes(EtgHandle* h, const uint8_t* mask, void* stream);

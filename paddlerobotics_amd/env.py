@@ -749,6 +749,8 @@ class BatchedQuadrupedEnv:
         a = None if action is None else self._f32(action, (self.num_envs, self.action_space.shape[0]), "action")   # NULL = zero residual
         df = self._donef_bytes(donef)
         term = bool(terminal_obs) and self.auto_reset
+        if int(groups) > 1:
+            self._groups_ok("step(groups=G)")   # (refused before the push stream moves: a refused call changes nothing)
         if self._rand_force:
             self._random_pushes()
         # auto_reset: robots whose episode just ended start the next one inside the same call (settle cache -> state, control
@@ -976,7 +978,8 @@ class BatchedQuadrupedEnv:
     def rollout_openloop(self, n_steps, out=None):
         """n_steps control steps with zero residual action (pretrain.py:129-154) enqueued back to
         back; returns (episode_return[N], episode_len[N]) since the last reset, alive-masked.  out = (ret float32 [N],
-        len int32 [N]) reuses the caller's buffers."""
+        len int32 [N]) reuses the caller's buffers.  With random pushes (random_param['random_force']) the steps are n_steps
+        calls of step(None), each of which samples the pushes: the fused launch samples none."""
         if self.auto_reset:
             raise ValueError("rollout_openloop does not restart finished robots: step an auto_reset env with step(), or roll out an "
                              "env made without auto_reset")
@@ -988,6 +991,13 @@ class BatchedQuadrupedEnv:
         else:
             ret = torch.empty(self.num_envs, device=self.device)           # every entry is written by the kernel: no fill launch
             ln = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        if self._rand_force:
+            # the fused launch samples no pushes (include/etgsim.h: etg_random_pushes is one call per control step): it would hold
+            # an active push for all its steps and start none, so a random_force env takes the stepping loop
+            for _ in range(int(n_steps)):
+                self.step(None, want_info=False)
+            _lib.check(self._lib.etg_episode_stats(self._h, _ptr(ret), _ptr(ln), self._stream()))
+            return ret, ln
         _lib.check(self._lib.etg_rollout_openloop(self._h, int(n_steps), _ptr(self.obs), _ptr(ret), _ptr(ln),
                                                   self._stream()))
         return ret, ln
@@ -1099,7 +1109,8 @@ class BatchedQuadrupedEnv:
         outputs to keep -- any of "joint_angle" [T,N,12], "obs-IMU" [T,N,6] (the info columns the dynamics-identification
         replay reads, Dynamic_parallel_model.py:63-64), "obs" [T,N,49], "reward" [T,N], "done" [T,N].
         Returns (episode_return[N], episode_len[N], rec dict).  The same source as T calls of step() in another kernel: equal to
-        rounding noise (the compiler contracts multiply-adds differently), not bit for bit."""
+        rounding noise (the compiler contracts multiply-adds differently), not bit for bit.  FusedKernelUnavailable (nothing
+        changed): auto_reset, HYBRID mode, random pushes, recorded observations under sensor noise."""
         N = self.num_envs
         a = torch.as_tensor(actions, dtype=torch.float32, device=self.device)
         if a.dim() == 2:
@@ -1112,6 +1123,8 @@ class BatchedQuadrupedEnv:
             raise FusedKernelUnavailable("rollout_actions does not restart finished robots: use an env without auto_reset")
         if self.motor_mode == 2:
             raise FusedKernelUnavailable("rollout_actions: POSITION / TORQUE commands only (HYBRID rows have 60 columns)")
+        if self._rand_force:   # (the launch would sample none: an active push held for every step, no new one started)
+            raise FusedKernelUnavailable("rollout_actions steps a known tape in one launch: random pushes are not covered")
         if "obs" in record and getattr(self, "_noise_on", False):
             raise FusedKernelUnavailable("rollout_actions records observations without sensor noise: switch it off or step")
         T = a.shape[0]
