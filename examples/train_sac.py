@@ -6,6 +6,7 @@ actor the simulator uses being the one the learner has just updated (learner.pol
 
 Usage: python examples/train_sac.py [--num-envs 4096] [--iters 200] [--collect-steps 1] [--collect-chunk 0] [--utd 4]
                                     [--eval-every 50] [--out sac.pt] [--checkpoint DIR [--resume]] [--log-episodes] [--n-step 1]
+                                    [--height-scan] [--task NAME]
 --collect-chunk K: the --collect-steps control steps of an iteration run K to a launch (env.collect_policy) instead of one
 launch per step; 0 (the default) is the per-step path.
 --utd: updates per control step (the reference does one update of 256 rows per transition of its single robot).
@@ -17,7 +18,10 @@ mean_{term}, success_rate) averaged over the training episodes that finished sin
 monitor is saved (monitor.pt) and resumed too.
 --n-step N: the memory receives N-step rows (nstep.NStepWriter with the learner's gamma: the discounted sum of N rewards, the
 observation N steps later, terminal * gamma^(N-1)), so that one update carries reward N control steps back; 1 (the default)
-takes the 1-step path as it was.  With --checkpoint the writer is saved (nstep.pt) and resumed too."""
+takes the 1-step path as it was.  With --checkpoint the writer is saved (nstep.pt) and resumed too.
+--height-scan: a perceptive learner -- the envs are made with sensor_mode={"height_scan": 1} (the default 5 x 3 grid of terrain
+clearances, heightscan.py) on --task (default then "stairstair"), and DeviceSAC learns on 49 + 15 = 64 columns.  The fused
+collection kernels do not compute these columns, so collect_continuous takes its stepping path."""
 import argparse
 import os
 import sys
@@ -73,11 +77,16 @@ def main():
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--log-episodes", action="store_true")      # per-episode reward terms and success rate of the training episodes
     ap.add_argument("--n-step", type=int, default=1)            # rows of this many control steps (1: the 1-step path as it was)
+    ap.add_argument("--height-scan", action="store_true")       # the 15 terrain height scan columns after the 49-float row
+    ap.add_argument("--task", type=str, default=None)           # default: "stairstair" with --height-scan, else "ground"
     args = ap.parse_args()
     if args.resume and not args.checkpoint:
         ap.error("--resume needs --checkpoint DIR")
-    env = make_env("Quadrupedal", num_envs=args.num_envs, device=args.device, auto_reset=True)
-    evl = make_env("Quadrupedal", num_envs=min(args.num_envs, 256), device=args.device)
+    kw = {"task": args.task or ("stairstair" if args.height_scan else "ground")}
+    if args.height_scan:
+        kw["sensor_mode"] = {"height_scan": 1}
+    env = make_env("Quadrupedal", num_envs=args.num_envs, device=args.device, auto_reset=True, **kw)
+    evl = make_env("Quadrupedal", num_envs=min(args.num_envs, 256), device=args.device, **kw)
     obs_dim, act_dim = env.observation_space.shape[0], env.action_space.shape[0]
     learner = DeviceSAC(obs_dim, act_dim, gamma=0.99, tau=0.005, alpha=0.2, actor_lr=3e-4, critic_lr=3e-4, device=args.device)
     rpm = DeviceReplayMemory(args.memory_size, obs_dim, act_dim, device=args.device)

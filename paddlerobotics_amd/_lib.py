@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h, include/etgsim_terminal.h,
-include/etgsim_render.h, include/etgsim_sac.h, include/etgsim_bc.h, include/etgsim_snapshot.h, include/etgsim_collect.h, include/etgsim_monitor.h and include/etgsim_nstep.h
+include/etgsim_render.h, include/etgsim_sac.h, include/etgsim_bc.h, include/etgsim_snapshot.h, include/etgsim_collect.h, include/etgsim_monitor.h, include/etgsim_nstep.h and include/etgsim_heightscan.h
 (paddlerobotics_amd/csrc/libetgsim.so).
 
 There is no CPU fallback: if the library is missing this module raises, and if no HIP
@@ -42,6 +42,8 @@ COLLECT_SYMBOLS = ["etg_collect_policy"]
 MONITOR_SYMBOLS = ["etg_collect_policy_info", "etg_monitor_feed"]
 # ... and include/etgsim_nstep.h
 NSTEP_SYMBOLS = ["etg_nstep_feed", "etg_nstep_flush"]
+# ... and include/etgsim_heightscan.h
+HEIGHTSCAN_SYMBOLS = ["etg_scan_pose", "etg_height_scan_at", "etg_height_scan"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 
@@ -118,6 +120,9 @@ def load():
     lib.etg_monitor_feed.argtypes = [i32, i32, i32, C.c_longlong, C.c_float, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.etg_nstep_feed.argtypes = [i32, i32, i32, i32, C.c_float, i32, C.c_longlong, i32, i32] + [vp] * 18 + [C.c_longlong, vp, vp, vp]
     lib.etg_nstep_flush.argtypes = [i32, i32, i32, C.c_float, i32, C.c_longlong, i32, i32] + [vp] * 11 + [C.c_longlong, vp, vp, vp]
+    lib.etg_scan_pose.argtypes = [vp, vp, vp]
+    lib.etg_height_scan_at.argtypes = [vp, vp, vp, i32, vp, i32, C.c_float, C.c_float, vp, vp]
+    lib.etg_height_scan.argtypes = [vp, vp, i32, C.c_float, C.c_float, vp, vp]
     lib.etg_step_autoreset_terminal.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_extra_sensors_terminal.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.etg_render.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]

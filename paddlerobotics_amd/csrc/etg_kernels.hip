@@ -2349,6 +2349,8 @@ ETG_INSTP4(k_rollout_policy4, true, 3, 4, 5, 6, 7, 1, ETG_ARGS_POLICY)
 #include "../../include/etgsim_render.h"
 #include "snapshot_core.h"
 #include "../../include/etgsim_snapshot.h"
+#include "scan_core.h"
+#include "../../include/etgsim_heightscan.h"
 #include <string.h>
 
 // ====================================================================== C ABI
@@ -3240,6 +3242,45 @@ extern "C" int etg_render(EtgHandle* h, const float* state, const int* env_ids, 
   }
   const render::RenderScene S = render::make_render_scene(h->K, h->M, h->hf, h->hf_lo, h->hf_hi);
   HIP_TRY(etg_render_launch(S, state, env_ids, n, view, proj, width, height, rgba, depth, seg, s));
+  return ETG_OK;
+}
+
+// the terrain height scan (include/etgsim_heightscan.h): argument checks here, the kernels in etg_heightscan.hip
+static int scan_args(const char* fn, const EtgHandle* h, bool live, const void* pose, long long M, const float* points, int P, float offset,
+                     float clip, const float* out) {
+  const std::string f(fn);
+  if (!h) return fail(ETG_ERR_BAD_ARG, f + ": null handle");
+  if ((!live && !pose) || !points || !out) return fail(ETG_ERR_BAD_ARG, f + ": null argument");
+  if (M < 1) return fail(ETG_ERR_BAD_ARG, f + ": M must be at least 1");
+  if (P < 1 || P > ETG_HEIGHT_SCAN_MAX_POINTS) return fail(ETG_ERR_BAD_ARG, f + ": P must be in 1..64");
+  if (M * P >= (1ll << 31) - 256) return fail(ETG_ERR_BAD_ARG, f + ": M * P must be below 2^31 - 256");
+  if (clip < 0.0f) return fail(ETG_ERR_BAD_ARG, f + ": clip must not be negative");
+  if (live && !h->was_reset) return fail(ETG_ERR_STATE, f + ": call etg_reset first");
+  if (h->K.terrain != 0 && !h->K.hf) return fail(ETG_ERR_STATE, f + ": call etg_set_heightfield first");
+  return ETG_OK;
+}
+
+extern "C" int etg_scan_pose(EtgHandle* h, float* pose, void* stream) {
+  if (!h) return fail(ETG_ERR_BAD_ARG, "etg_scan_pose: null handle");
+  if (!pose) return fail(ETG_ERR_BAD_ARG, "etg_scan_pose: null argument");
+  if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_scan_pose: call etg_reset first");
+  CHECK_HANDLE(h);
+  HIP_TRY(etg_scan_pose_launch(h->D.base, h->N, pose, (hipStream_t)stream));
+  return ETG_OK;
+}
+
+extern "C" int etg_height_scan_at(EtgHandle* h, const float* pose, const int32_t* env_ids, int M, const float* points, int P, float offset,
+                                  float clip, float* out, void* stream) {
+  if (int rc = scan_args("etg_height_scan_at", h, false, pose, M, points, P, offset, clip, out)) return rc;
+  CHECK_HANDLE(h);
+  HIP_TRY(etg_height_scan_launch(h->K, h->D.base, pose, env_ids, M, points, P, offset, clip, out, (hipStream_t)stream));
+  return ETG_OK;
+}
+
+extern "C" int etg_height_scan(EtgHandle* h, const float* points, int P, float offset, float clip, float* out, void* stream) {
+  if (int rc = scan_args("etg_height_scan", h, true, nullptr, h ? h->N : 1, points, P, offset, clip, out)) return rc;
+  CHECK_HANDLE(h);
+  HIP_TRY(etg_height_scan_launch(h->K, h->D.base, nullptr, nullptr, h->N, points, P, offset, clip, out, (hipStream_t)stream));
   return ETG_OK;
 }
 

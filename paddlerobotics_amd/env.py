@@ -21,6 +21,7 @@ import torch
 
 from . import a1_model as A
 from . import _lib
+from . import heightscan as _hs
 from .etg import ETG_layer, Opt_with_points
 from .terrain import TERRAIN_TASKS, make_task_heightfield
 
@@ -195,6 +196,8 @@ class EnvSnapshot:
 
 
 class BatchedQuadrupedEnv:
+    _scan_P = 0                      # scan columns in the view (sensor_mode["height_scan"]); set per env in __init__
+
     def __init__(self, num_envs=1, device="cuda:0", task="ground", motor_control_mode=None, render=False,
                  sensor_mode=None, normal=1, dynamic_param=None, reward_param=None, ETG=1, ETG_T=0.5,
                  reward_p=5.0, ETG_path="", random_param=None, ETG_H=20, vel_d=0.5, step_y=0.05,
@@ -206,7 +209,7 @@ class BatchedQuadrupedEnv:
                  random_force_range=(5.0, 25.0), seed=0, enable_clip_motor_commands=False,
                  observation_noise_stdev=None, body_contacts=2, body_friction=0.5, knee_radius=0.02, joint_limits=True,
                  auto_reset=False, random_dynamics_refresh=256, warmstart=0.1, warmstart_friction=0.0, contact_slop=1e-5,
-                 foot_restitution=0.0, motor_torque_limits=None, solver_preset=None, body_blend=1e-3, **unused):
+                 foot_restitution=0.0, motor_torque_limits=None, solver_preset=None, body_blend=1e-3, height_scan=None, **unused):
         # render=True (train.py:278,305: evaluation) only opens pybullet's GUI in the reference; frames are taken explicitly
         # there (p.getCameraImage) and here (render(), SingleRobotEnv.getCameraImage), so it changes nothing about stepping
         if int(ETG_H) != A.RBF_H:
@@ -245,6 +248,19 @@ class BatchedQuadrupedEnv:
         self._hist_T = int(rnn.get("time_steps", 0))
         self._hist_dt = int(rnn.get("time_interval", 1)) if self._hist_T > 0 else 1
         self._hist_mode = rnn.get("mode", "stack")
+        # the terrain height scan (heightscan.py, include/etgsim_heightscan.h): height_scan=dict(xs=, ys=, offset=, clip=) sets the
+        # grid of scan_pose() / height_scan() / height_scan_at(); sensor_mode["height_scan"] appends its P columns to the view
+        hs = dict(height_scan or {})
+        unknown = set(hs) - {"xs", "ys", "offset", "clip"}
+        if unknown:
+            raise ValueError("height_scan has the keys xs, ys, offset and clip, not %s" % ", ".join(sorted(unknown)))
+        self._scan_grid = _hs.scan_grid(hs.get("xs", _hs.DEFAULT_XS), hs.get("ys", _hs.DEFAULT_YS))
+        self._scan_offset, self._scan_clip = float(hs.get("offset", _hs.DEFAULT_OFFSET)), float(hs.get("clip", _hs.DEFAULT_CLIP))
+        self._scan_P = len(self._scan_grid) if (sensor_mode or {}).get("height_scan") else 0
+        self._scan_pts = self._scan_buf = None
+        if self._scan_P and self._hist_T > 0:
+            raise NotImplementedError("sensor_mode['height_scan'] together with observation history (sensor_mode['RNN']) is "
+                                      "not covered: the history ring holds no scan columns")
         self._hist = None
         self._hist_head = 0
         self._last_seq = None
@@ -299,7 +315,7 @@ class BatchedQuadrupedEnv:
             # foot positions are pulled in to y = -+step_y so the feet land on the beam (right legs negative y)
             for leg in range(4):
                 self.model.base_foot[3 * leg + 1] = (-1.0 if leg % 2 == 0 else 1.0) * float(step_y)
-        d = len(self._cols) + len(self._xcols)
+        d = len(self._cols) + len(self._xcols) + self._scan_P
         if self._hist_T > 0:
             shape = (d * (self._hist_T + 1),) if self._hist_mode == "stack" else (self._hist_T + 1, d)
         else:
@@ -519,6 +535,70 @@ class BatchedQuadrupedEnv:
             o = torch.cat([o, extra.index_select(1, self._xcol_idx)], dim=1)
         return o
 
+    # ---- the terrain height scan (include/etgsim_heightscan.h; heightscan.py) ---------------------------------------------
+    def _scan_points(self, points):
+        """the env's grid as a device tensor [P,2], or the caller's points"""
+        if points is None:
+            if self._scan_pts is None:
+                self._scan_pts = torch.as_tensor(self._scan_grid, device=self.device).contiguous()
+            return self._scan_pts
+        p = torch.as_tensor(points, dtype=torch.float32, device=self.device).contiguous()
+        if p.dim() != 2 or p.shape[1] != 2 or not 1 <= p.shape[0] <= _hs.MAX_POINTS:
+            raise ValueError("points must have shape [P,2] with 1 <= P <= %d" % _hs.MAX_POINTS)
+        return p
+
+    def scan_pose(self):
+        """x, y, z, yaw [N,4] of every robot's base, now (etg_scan_pose): the rows height_scan_at() takes"""
+        pose = torch.empty(self.num_envs, _hs.POSE_DIM, device=self.device)
+        _lib.check(self._lib.etg_scan_pose(self._h, _ptr(pose), self._stream()))
+        return pose
+
+    def height_scan(self, points=None, out=None):
+        """The live terrain scan [N,P] (etg_height_scan): column j is the clearance of the robot's base above its terrain at
+        point j of the yaw-aligned grid -- clamp(z - H(X_j, Y_j) - offset, -clip, clip), no noise, no latency.  points [P,2]
+        (a forward, b left; metres) replaces the env's grid (make_env(height_scan=dict(xs=, ys=, offset=, clip=)); the
+        default is heightscan.DEFAULT_XS x DEFAULT_YS, x-major)."""
+        pts = self._scan_points(points)
+        if out is None:
+            out = torch.empty(self.num_envs, pts.shape[0], device=self.device)
+        _lib.check(self._lib.etg_height_scan(self._h, _ptr(pts), int(pts.shape[0]), C.c_float(self._scan_offset),
+                                             C.c_float(self._scan_clip), _ptr(out), self._stream()))
+        self._keep_scan = pts
+        return out
+
+    def height_scan_at(self, pose, env_ids=None, points=None):
+        """The scan for given poses (etg_height_scan_at): pose [..., 4] rows x, y, z, yaw (scan_pose()'s layout) -> [..., P].
+        env_ids (same leading shape, integers): the robot whose terrain band each row reads; None: flattened row i is robot
+        i % N, so a record [K,N,4] of K steps is taken as it is.  A row whose id names no robot is NaN."""
+        pts = self._scan_points(points)
+        p = torch.as_tensor(pose, dtype=torch.float32, device=self.device).contiguous()
+        if p.dim() < 1 or p.shape[-1] != _hs.POSE_DIM or p.numel() == 0:
+            raise ValueError("pose must have shape [..., 4] (x, y, z, yaw) with at least one row")
+        M = p.numel() // _hs.POSE_DIM
+        ids = None
+        if env_ids is not None:
+            ids = torch.as_tensor(env_ids, device=self.device).to(torch.int32).contiguous()
+            if ids.numel() != M:
+                raise ValueError("env_ids must name one robot per pose row")
+        out = torch.empty(*p.shape[:-1], pts.shape[0], device=self.device)
+        _lib.check(self._lib.etg_height_scan_at(self._h, _ptr(p), _ptr(ids), int(M), _ptr(pts), int(pts.shape[0]),
+                                                C.c_float(self._scan_offset), C.c_float(self._scan_clip), _ptr(out), self._stream()))
+        self._keep_scan = (p, ids, pts)
+        return out
+
+    def _scan_live(self):
+        """the scan columns of the view: the env's grid at the live state, in the env's own buffer"""
+        if self._scan_buf is None:
+            self._scan_buf = torch.zeros(self.num_envs, self._scan_P, device=self.device)
+        return self.height_scan(out=self._scan_buf)
+
+    def _scan_of_info(self):
+        """the scan columns at the pose the last step's info rows hold: a robot's pose BEFORE a restart inside the step (the
+        control step writes ETG_INFO_BASE / ETG_INFO_RPY before the restart phase runs)"""
+        a, y = A.INFO_SLICES["base"][0], A.INFO_SLICES["rpy"][0] + 2
+        pose = torch.cat([self.info_buf[:, a:a + 3], self.info_buf[:, y:y + 1]], dim=1)
+        return self.height_scan_at(pose)
+
     def _obs_view(self, reset_mask=None, first=False):
         """the observation the caller sees: sensor_mode column selection, then (optionally) the history stack.
         reset_mask: uint8 [N] of the robots that were just reset (None = all, with first=True)."""
@@ -527,6 +607,8 @@ class BatchedQuadrupedEnv:
             _lib.check(self._lib.etg_extra_sensors(self._h, _ptr(self.obs), _ptr(self.extra), self._stream()))
             extra = self.extra
         o = self._row_view(self.obs, extra)
+        if getattr(self, "_scan_P", 0):   # sensor_mode["height_scan"]: the scan columns come last
+            o = torch.cat([o, self._scan_live()], dim=1)
         if self._hist_T == 0:
             return o
         H = self._hist_T * self._hist_dt
@@ -641,6 +723,8 @@ class BatchedQuadrupedEnv:
         return [(a, min(a + per, self.num_envs)) for a in range(0, self.num_envs, per)]
 
     def _groups_ok(self, what):
+        if self._scan_P:
+            raise FusedKernelUnavailable("%s: height scan columns are not covered (sensor_mode['height_scan'])" % what)
         if self.auto_reset or self._rand_force or self._hist_T > 0 or len(self._xcols) > 0:
             raise ValueError("%s: sub-batches are for envs without auto_reset, random pushes, observation history and extra sensors" % what)
 
@@ -758,20 +842,22 @@ class BatchedQuadrupedEnv:
         # step's, info["reset"] (= done) marks them.  The done bytes are read on the device: no host synchronisation.
         # With random_dynamics the reset robots first draw new parameters, which needs the masked calls of reset().
         fused_reset = self.auto_reset and (not self._rand_dyn or self._nx_on)   # (_nx_on: the next episodes' dynamics are prepared)
+        # (a scan env always takes the info rows: they hold the pose of a restarting robot before its restart, _scan_of_info)
+        ib = self.info_buf if (want_info or self._scan_P) else None
         if int(groups) > 1:
             self._step_grouped(a, df, want_info, groups)
         elif fused_reset and term:   # the same launches and results as etg_step_autoreset, plus the rows before the restart
             t_obs, t_ctx, t_extra = self._terminal_buffers()
             _lib.check(self._lib.etg_step_autoreset_terminal(self._h, _ptr(a), _ptr(df), _ptr(self.obs), _ptr(t_obs), _ptr(t_ctx),
                                                              _ptr(self.reward), _ptr(self.done),
-                                                             _ptr(self.info_buf) if want_info else None, self._stream()))
+                                                             _ptr(ib), self._stream()))
             if t_extra is not None:
                 _lib.check(self._lib.etg_extra_sensors_terminal(self._h, _ptr(t_obs), _ptr(t_ctx), _ptr(self.done), _ptr(t_extra),
                                                                 self._stream()))
         else:
             step_fn = self._lib.etg_step_autoreset if fused_reset else self._lib.etg_step
             _lib.check(step_fn(self._h, _ptr(a), _ptr(df), _ptr(self.obs), _ptr(self.reward), _ptr(self.done),
-                               _ptr(self.info_buf) if want_info else None, self._stream()))
+                               _ptr(ib), self._stream()))
         self._keep_step = (a, df)
         info = self._info() if want_info else {}
         if self.auto_reset:
@@ -782,6 +868,8 @@ class BatchedQuadrupedEnv:
                     if self._xcol_idx is not None:
                         _lib.check(self._lib.etg_extra_sensors(self._h, _ptr(self.obs), _ptr(self.extra), self._stream()))
                     tv = self._row_view(self.obs, self.extra).clone()
+                    if self._scan_P:
+                        tv = torch.cat([tv, self._scan_live()], dim=1)
                 self._reset_mask = self.done.clone()
                 self.reset(env_ids=self._reset_mask, _keep_offsets=True)
             if want_info:
@@ -797,6 +885,8 @@ class BatchedQuadrupedEnv:
                 self._last_view = self._obs_view()
                 if term:
                     tv = self._row_view(t_obs, t_extra)
+                    if self._scan_P:
+                        tv = torch.cat([tv, self._scan_of_info()], dim=1)
             if term:
                 info["terminal_obs"] = tv
             if self._nx_on:
@@ -820,6 +910,8 @@ class BatchedQuadrupedEnv:
             return "observation history (sensor_mode['RNN']) is not covered"
         if self._xcols:
             return "extra sensor columns are not covered"
+        if self._scan_P:
+            return "height scan columns are not covered (sensor_mode['height_scan']: step() appends them after the launch)"
         if getattr(self, "_noise_on", False):
             return "sensor noise is not covered"
         if self._rand_force:
@@ -1015,6 +1107,9 @@ class BatchedQuadrupedEnv:
               and self._hist_T == 0 and not self._rand_force and policy.obs_dim == len(self._cols)
               and policy.action_dim == A.NUM_MOTORS and not self.auto_reset
               and self.cfg.body_contacts != 3)   # (three body rows per leg: no closed-loop instantiation)
+        if fused and self._scan_P:
+            raise FusedKernelUnavailable("rollout_policy(fused=True): height scan columns are not covered (sensor_mode['height_scan'])")
+        ok = ok and not self._scan_P
         if fused and not ok:
             raise FusedKernelUnavailable("rollout_policy(fused=True): this configuration is outside the fused closed-loop kernel")
         if fused is None:
@@ -1078,6 +1173,8 @@ class BatchedQuadrupedEnv:
         final_obs [N,49]).  The data half of run_EStrain_episode with es_rpm (train.py:213-249) at the fused kernel's speed;
         replay.store_recorded() moves the rows of live robots into a DeviceReplayMemory.  Needs the configuration the
         fused kernel needs (16-lane mapping, num_envs % 16 == 0, the full 49-float observation, POSITION / TORQUE mode)."""
+        if self._scan_P:
+            raise FusedKernelUnavailable("rollout_policy_record: height scan columns are not covered (sensor_mode['height_scan'])")
         if self.auto_reset:
             raise FusedKernelUnavailable("rollout_policy_record does not restart finished robots: use an env without auto_reset")
         if not (self.lanes_per_robot == 16 and self.num_envs % 16 == 0 and self.motor_mode != 2 and self._hist_T == 0
@@ -1272,8 +1369,11 @@ class BatchedQuadrupedEnv:
         h = hashlib.sha256()
         h.update(bytes(self.cfg))
         h.update(bytes(self.model))
-        h.update(repr((self.task, self._cols, self._xcols, self._hist_T, self._hist_dt, self._hist_mode, self.auto_reset,
-                       self._rand_dyn, self._rand_force, self._rand_dyn_scale, self.lanes_per_robot)).encode())
+        view = (self.task, self._cols, self._xcols, self._hist_T, self._hist_dt, self._hist_mode, self.auto_reset,
+                self._rand_dyn, self._rand_force, self._rand_dyn_scale, self.lanes_per_robot)
+        if self._scan_P:   # (an env without the scan columns keeps the digest it had before they existed)
+            view += (("height_scan", self._scan_grid.tolist(), self._scan_offset, self._scan_clip),)
+        h.update(repr(view).encode())
         cfg = h.hexdigest()
         t = hashlib.sha256()
         if self._hf is not None:
