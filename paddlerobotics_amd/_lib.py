@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h, include/etgsim_terminal.h,
-include/etgsim_render.h, include/etgsim_sac.h, include/etgsim_bc.h, include/etgsim_snapshot.h, include/etgsim_collect.h, include/etgsim_monitor.h, include/etgsim_nstep.h and include/etgsim_heightscan.h
+include/etgsim_render.h, include/etgsim_sac.h, include/etgsim_bc.h, include/etgsim_snapshot.h, include/etgsim_collect.h, include/etgsim_monitor.h, include/etgsim_nstep.h, include/etgsim_heightscan.h and include/etgsim_ppo.h
 (paddlerobotics_amd/csrc/libetgsim.so).
 
 There is no CPU fallback: if the library is missing this module raises, and if no HIP
@@ -44,6 +44,10 @@ MONITOR_SYMBOLS = ["etg_collect_policy_info", "etg_monitor_feed"]
 NSTEP_SYMBOLS = ["etg_nstep_feed", "etg_nstep_flush"]
 # ... and include/etgsim_heightscan.h
 HEIGHTSCAN_SYMBOLS = ["etg_scan_pose", "etg_height_scan_at", "etg_height_scan"]
+# ... and include/etgsim_ppo.h
+PPO_SYMBOLS = ["etg_ppo_create", "etg_ppo_destroy", "etg_ppo_set_hyper", "etg_ppo_load", "etg_ppo_store", "etg_ppo_load_opt",
+               "etg_ppo_store_opt", "etg_ppo_sync_policy", "etg_ppo_prepare", "etg_ppo_gae", "etg_ppo_norm_adv", "etg_ppo_fetch",
+               "etg_ppo_learn", "etg_ppo_learn_rows", "etg_ppo_grads"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 
@@ -152,6 +156,21 @@ def load():
     lib.etg_bc_learn_replay.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.etg_bc_grads.argtypes = [vp, vp, vp, i32, vp, vp, C.POINTER(vp), vp]
     lib.etg_bc_sync_policy.argtypes = [vp, vp, vp]
+    lib.etg_ppo_create.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+    lib.etg_ppo_destroy.argtypes = [vp]
+    lib.etg_ppo_set_hyper.argtypes = [vp] + [C.c_double] * 4
+    lib.etg_ppo_load.argtypes = [vp, C.POINTER(vp), i32, vp]
+    lib.etg_ppo_store.argtypes = [vp, C.POINTER(vp), i32, vp]
+    lib.etg_ppo_load_opt.argtypes = [vp, vp, vp, vp, vp]
+    lib.etg_ppo_store_opt.argtypes = [vp, vp, vp, vp, vp]
+    lib.etg_ppo_sync_policy.argtypes = [vp, vp, vp]
+    lib.etg_ppo_prepare.argtypes = [vp, vp, vp, vp, i32, vp]
+    lib.etg_ppo_gae.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp]
+    lib.etg_ppo_norm_adv.argtypes = [vp, vp, i32, vp]
+    lib.etg_ppo_fetch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.etg_ppo_learn.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+    lib.etg_ppo_learn_rows.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+    lib.etg_ppo_grads.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp), vp]
     lib.etg_rollout_actions.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_prepare_next_dynamics.argtypes = [vp, vp, vp, vp]
     lib.etg_next_dynamics_pending.argtypes = [vp, vp, vp]

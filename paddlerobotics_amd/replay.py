@@ -217,6 +217,13 @@ def bootstrap_mask(done, episode_steps):
     return 1.0 - done.view(-1).to(torch.float32)
 
 
+def bootstrap_flags(done, episode_steps):
+    """bootstrap_mask per robot, for robots that do not share an episode clock (continuous collection): done [N] bool,
+    episode_steps [N] the 1-based step of each robot's OWN episode -> float32 [N]"""
+    keep = 1.0 - done.view(-1).to(torch.float32)
+    return torch.where(episode_steps.view(-1) >= BOOTSTRAP_ALWAYS_FROM, torch.ones_like(keep), keep)
+
+
 def _scalar_info_columns(info_keys):
     """info keys that can be summed per episode: the scalar (one-column) entries of a1_model.INFO_SLICES; like the reference's
     `if key in info.keys()` (train.py:150-151) anything else is skipped, on both storage paths."""
@@ -405,7 +412,7 @@ def collect_continuous(env, rpm, n_steps, policy=None, action_bound=0.3, mode="s
             d = done.view(-1).to(torch.bool)
             run_ret = run_ret + reward
             run_len = run_len + 1                       # the 1-based episode step of this transition, per robot
-            terminal = torch.where(run_len >= BOOTSTRAP_ALWAYS_FROM, torch.ones_like(reward), 1.0 - d.to(torch.float32))
+            terminal = bootstrap_flags(d, run_len)
             if nstep is None:
                 rpm.append_batch(obs, action, reward, next_obs, terminal)
             else:
