@@ -66,6 +66,30 @@ def short(kw):
     return {k: (v if k != "heightfield" else "64x64") for k, v in kw.items()}
 
 
+def trial_verdict(eg, ref, loose, heightfield, finite=True, tally=None):
+    """The fuzz trial rule, in one place for tests/test_emu_fuzz.py, tools/fuzz_parity.py and the negative controls
+    (tests/parity_controls.py) -> dict(finite, robots, median) of booleans; a trial passes when all are true.
+
+    eg: per robot, the worst joint gap of the code under test to the fp64 oracle over the trial; loose: the floor's factor for
+    a looser residual threshold (setup_trial); heightfield: the trial runs on a random heightfield.
+      * tally is None (the CPU fuzz): ref = the fp32 oracle's gap per robot.  robots: the share within 1e-4 x loose + 4 x ref is
+        at least 0.9 (0.6 on a heightfield); median: the median gap (the lower quartile on a heightfield) is below
+        max(5e-5 x loose, 4 x the same statistic of ref).
+      * tally = tests.parity_util.sens_tally(eg, ref, 1e-4 x loose) (the GPU fuzz): ref = the ensemble's spread per robot.
+        robots: no more outside than the tally allows (on a heightfield: the share inside is at least 0.6); median: over the
+        quarter of the robots whose ensemble stayed closest together, below max(5e-5 x loose, 4 x their median spread)."""
+    eg, ref = np.asarray(eg, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    need = 0.6 if heightfield else 0.9
+    if tally is None:
+        frac = float(np.mean(eg <= 1e-4 * loose + 4.0 * ref))
+        mid = (lambda x: np.percentile(x, 25)) if heightfield else np.median
+        return dict(finite=bool(finite), robots=bool(frac >= need), median=bool(mid(eg) < max(5e-5 * loose, 4.0 * mid(ref))))
+    frac = 1.0 - len(tally["bad"]) / float(len(eg))
+    calm = np.argsort(ref)[:max(4, len(eg) // 4)]
+    robots_ok = (frac >= need) if heightfield else (len(tally["bad"]) <= tally["allowed"])
+    return dict(finite=bool(finite), robots=bool(robots_ok), median=bool(np.median(eg[calm]) < max(5e-5 * loose, 4.0 * np.median(ref[calm]))))
+
+
 
 
 def trial_rng(seed, trial):

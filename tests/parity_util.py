@@ -23,6 +23,20 @@ robots for that reason without looking at them; here every robot is held to its 
     one robot of `warmstart_085 lanes 4` -- restarted from the GPU's own states, the GPU stays on the fp64 oracle's branch at
     every step and it is the fp32 ORACLE that parts, by the same 1.1e-3 rad).  Every outside robot is listed in the [parity]
     line.  Without the ensemble's per-member record (a spread array the test built some other way) no robot may be outside.
+  * An outside robot is excused for PARTING, not for being anywhere: it may sit no further off than members of the ensemble sit
+    when they part -- 4 x the larger of this ensemble's own largest member-to-nominal gap on the same columns and the lone parting
+    on record for the column group (LONE_PARTING: the fp32 oracle's 1.09e-3 rad above).  The suite-wide alternative, 4 x the
+    largest member gap of a clean run of the -m gpu suite, is set by the chaotic scenes (joints 4.8e-2 rad where joints ride
+    their stops, 2.8e-2 under torque commands: profiles/parity_controls.txt) and would let one robot sit 0.19 rad off on a
+    calm scene; with the scene's own partings in the cap a robot fed an action 1e-2 rad off (ending 1.4e-2 rad away) is red.
+  * The calm quartile (the quarter of the robots whose ensemble stayed closest together) is held to what the REFERENCE does on
+    the same robots: 4 x the fp32 oracle's own median gap to the nominal there (under a bf16 policy: 4 x the ensemble's median
+    spread, whose members carry that arithmetic's input noise), next to the older max(half the floor, 4 x the median spread).
+    Over a clean run of the -m gpu suite the GPU's calm-quartile median is at most 2.4 x the fp32 oracle's (74 criterion lines,
+    profiles/parity_controls.txt); no absolute term is needed beyond the fp32 read-out of the states (READOUT).
+  * What these criteria can and cannot see is measured, not claimed: tests/parity_controls.py runs them against a device that is
+    right and an oracle with one parameter mis-set (negative controls), tests/test_parity_controls.py asserts that every control
+    the fp64 oracle alone puts in range is red, DESIGN.md "What the parity criteria can and cannot see" has the table.
   * `nearest_member(...)`: for ONE control step from a synchronised state (tests/test_gpu_parity5.py) the criterion is sharper:
     the GPU's result must lie within the floor of SOME member's result -- the step map is discontinuous, the GPU has to be on
     one of its branches.
@@ -34,18 +48,26 @@ import numpy as np
 from paddlerobotics_amd import a1_model as A
 
 NCPU = os.cpu_count() or 1
+# sens_robots, outside robots.  A robot that parts ALONE may be outside its allowance, but not further off than members of the
+# ensemble sit when they part: factor x the larger of THIS ensemble's largest member-to-nominal gap on the same columns and
+# the lone parting on record for the column group (a quantity of the reference alone).  Joint angles: 1.09e-3 rad, the fp32
+# oracle parting alone at step 7 of profiles/r06_outlier_ws085_lanes4.txt; the suite-wide figures this was chosen against are
+# in profiles/parity_controls.txt ("The reference over a clean run of the -m gpu suite").  Other column groups have no lone
+# parting on record: their cap is the ensemble's own largest member gap.
+LONE_PARTING = {repr(slice(13, 25)): 1.09e-3}
+READOUT = 2.0 ** -22   # the spacing of fp32 in [2, 4): a state read through an fp32 buffer is not closer to fp64 than that
 REPORT = []          # (what, n_robots, n_allowance, text): the tests' own tally (printed per line, summarised by conftest)
 ENSEMBLES = []       # every OracleEnsemble made (sens_robots finds the per-member record behind a spread array here)
 
 
-def _member_record(spread):
+def _member_record(spread, with_key=False):
     """the per-member worst gaps [M, n] whose maximum over the members IS the given spread array (the test accumulated
-    ens.spread(cols) over the same steps), or None"""
+    ens.spread(cols) over the same steps), or None; with_key: (record, the repr of the state columns it was taken over, the ensemble)"""
     for ens in reversed(ENSEMBLES[-4:]):
-        for per in ens._acc.values():
+        for key, per in ens._acc.items():
             if per.shape[1:] == np.shape(spread) and np.array_equal(per.max(0), spread):
-                return per
-    return None
+                return (per, key, ens) if with_key else per
+    return (None, None, None) if with_key else None
 
 
 def _oracle(n, dtype=np.float64, **kw):
@@ -178,23 +200,40 @@ def sens_tally(err_gpu, spread, floor, factor=4.0):
     if need.any():
         txt += " (their gaps %.1e .. %.1e, their ensemble spread %.1e .. %.1e)" % (err_gpu[need].min(), err_gpu[need].max(),
                                                                                    spread[need].min(), spread[need].max())
-    per = _member_record(spread)
+    per, cols, ens = _member_record(spread, with_key=True)
     allowed, loo, loo_txt = 0, None, ""
+    calm = np.argsort(spread)[:max(4, n // 4)]
+    calm_gap, calm_ref, member_max, lone, cap = float(np.median(err_gpu[calm])), None, None, 0.0, None
+    if per is not None:
+        # what the reference does on the same robots: member 0 is the fp32 build of the oracle (OracleEnsemble.members).  Under a
+        # policy evaluated on bf16 operands (rel_noise > 0) the members that carry THAT arithmetic's input noise are the reference.
+        fp32_level = getattr(ens, "rel_noise", 0.0) == 0.0
+        calm_ref = float(np.median(per[0][calm])) if fp32_level else float(np.median(spread[calm]))
+        member_max = float(per.max())
+        cap = factor * max(member_max, LONE_PARTING.get(cols, 0.0))
+        loo_txt = " | reference on %s: %s calm-quartile median %.2e (the GPU's %.2e), largest member gap %.2e" % (
+            cols, "fp32 oracle's" if fp32_level else "ensemble spread's", calm_ref, calm_gap, member_max)
     if per is not None and per.shape[0] >= 3:
         loo = []
         for m in range(per.shape[0]):
             rest = np.delete(per, m, axis=0).max(0)
-            loo.append(int((per[m] > floor + factor * rest).sum()))
+            alone = per[m] > floor + factor * rest
+            loo.append(int(alone.sum()))
+            if alone.any():
+                lone = max(lone, float(per[m][alone].max()))
         allowed = max(loo) + max(1, int(round(n / 64.0)))
-        loo_txt = " | the members judged alike against the rest of the ensemble: %s outside -> allowed %d" % (loo, allowed)
+        loo_txt += " | the members judged alike against the rest of the ensemble: %s outside (the furthest of them %.2e off) -> allowed %d" % (loo, lone, allowed)
     if bad.any():
-        loo_txt += " | the GPU's outside robots: " + ", ".join("#%d gap %.1e spread %.1e" % (i, err_gpu[i], spread[i]) for i in np.nonzero(bad)[0][:6])
-    return dict(n=n, need=int(need.sum()), bad=np.nonzero(bad)[0], allowed=allowed, loo=loo, text=txt, loo_text=loo_txt)
+        loo_txt += " | the GPU's outside robots (cap %s): " % ("%.1e" % cap if cap is not None else "-") + ", ".join(
+            "#%d gap %.1e spread %.1e" % (i, err_gpu[i], spread[i]) for i in np.nonzero(bad)[0][:6])
+    return dict(n=n, need=int(need.sum()), bad=np.nonzero(bad)[0], allowed=allowed, loo=loo, text=txt, loo_text=loo_txt,
+                calm=calm, calm_gap=calm_gap, calm_ref=calm_ref, member_max=member_max, lone=lone, cap=cap, cols=cols)
 
 
 def sens_robots(err_gpu, spread, floor, what, factor=4.0):
     """A robot is inside when err_gpu <= floor + factor * spread; the GPU may be outside on as many robots as the ensemble's
-    worst member is when judged the same way against the other members, plus one per 64 robots (module docstring).  Prints the
+    worst member is when judged the same way against the other members, plus one per 64 robots, none of them further off than
+    the cap; the calm quartile is held to factor x what the fp32 oracle does on the same robots (module docstring).  Prints the
     tally of the robots that needed the allowance and of those outside."""
     err_gpu, spread = np.asarray(err_gpu, dtype=np.float64), np.asarray(spread, dtype=np.float64)
     t = sens_tally(err_gpu, spread, floor, factor)
@@ -204,10 +243,19 @@ def sens_robots(err_gpu, spread, floor, what, factor=4.0):
     REPORT.append((what, n, t["need"], t["text"]))
     assert np.isfinite(err_gpu).all(), what
     assert len(t["bad"]) <= t["allowed"], (what, t["bad"].tolist(), err_gpu[t["bad"]].tolist(), spread[t["bad"]].tolist())
+    # an outside robot is excused for parting, not for being anywhere: it may not sit further off than members of the ensemble
+    # sit when they part (LONE_PARTING above)
+    if t["cap"] is not None and len(t["bad"]):
+        assert err_gpu[t["bad"]].max() <= t["cap"], (what, "outside robots beyond the cap", t["cap"], t["bad"].tolist(), err_gpu[t["bad"]].tolist())
     # a wrong kernel moves EVERY robot: the quarter of the robots whose ensemble stayed closest together is held to half the floor
-    # (or, where even those part -- torque commands, joints riding their stops --, to 4 x their own median spread)
-    calm = np.argsort(spread)[:max(4, n // 4)]
+    # (or, where even those part -- torque commands, joints riding their stops --, to 4 x their own median spread) ...
+    calm = t["calm"]
     assert np.median(err_gpu[calm]) < max(0.5 * floor, factor * float(np.median(spread[calm]))), (what, float(np.median(err_gpu[calm])), float(np.median(spread[calm])))
+    # ... and, where the ensemble's record is at hand, to what the REFERENCE does on the same robots: factor x the fp32 oracle's own
+    # median gap to the nominal on that quartile (half the floor is 50 x what a clean run needs; a base inertia 1 % off moves the
+    # median to 20 x the clean one and stayed under it -- profiles/parity_controls.txt).  READOUT: the states are read as fp32.
+    if t["calm_ref"] is not None:
+        assert t["calm_gap"] < factor * max(t["calm_ref"], READOUT), (what, "calm quartile", t["calm_gap"], t["calm_ref"])
 
 
 def one_step_verdict(gpu, nominal, members, floor, factor=4.0):
