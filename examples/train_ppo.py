@@ -7,6 +7,7 @@ has just updated (learner.policy).
 Usage: python examples/train_ppo.py [--num-envs 4096] [--iters 200] [--steps 24] [--epochs 5] [--minibatches 4]
                                     [--eval-every 20] [--out ppo.pt] [--checkpoint DIR [--resume]] [--log-episodes]
                                     [--height-scan] [--task NAME]
+                                    [--max-grad-norm X] [--clip-value C] [--target-kl KL [--kl-control stop|adaptive]]
 --checkpoint DIR: at every evaluation the whole run is written to DIR -- learner.pt (weights and optimizer state) and env.pt
 (env.state_dict(): every robot mid-episode) -- and --resume picks the run up from there.  There is no memory to save: a rollout
 is consumed by the iteration that collected it.
@@ -16,6 +17,10 @@ over the training episodes that finished since the previous one.  With --checkpo
 --height-scan: a perceptive learner -- the envs are made with sensor_mode={"height_scan": 1} on --task (default then
 "stairstair"), and DevicePPO learns on 49 + 15 = 64 columns.  The one-launch collection does not compute these columns, so
 collect_rollout takes its stepping path.
+--max-grad-norm / --clip-value / --target-kl: DevicePPO's controls (off by default) -- gradient-norm clipping per optimizer, PPO2's
+clipped value loss, and with --target-kl either early stopping of the iteration's updates (--kl-control stop, the default) or a
+KL-adaptive learning rate (adaptive).  All of it is decided on the device; the evaluation line then also prints lr_scale and
+how many updates have been applied (control_state(): one more read at a point that waits anyway).  learner.pt carries lr_scale.
 The checkpoint --out is the model's usual 20 tensors: it loads into MfmaPolicy, examples/evaluate_policy.py and
 DeviceBC.set_teacher unchanged."""
 import argparse
@@ -72,6 +77,10 @@ def main():
     ap.add_argument("--log-episodes", action="store_true")      # per-episode reward terms and success rate of the training episodes
     ap.add_argument("--height-scan", action="store_true")       # the 15 terrain height scan columns after the 49-float row
     ap.add_argument("--task", type=str, default=None)           # default: "stairstair" with --height-scan, else "ground"
+    ap.add_argument("--max-grad-norm", type=float, default=None)  # the controls: off by default
+    ap.add_argument("--clip-value", type=float, default=None)
+    ap.add_argument("--target-kl", type=float, default=None)
+    ap.add_argument("--kl-control", choices=("stop", "adaptive"), default="stop")
     args = ap.parse_args()
     if args.resume and not args.checkpoint:
         ap.error("--resume needs --checkpoint DIR")
@@ -83,7 +92,8 @@ def main():
     obs_dim, act_dim = env.observation_space.shape[0], env.action_space.shape[0]
     rows = args.steps * args.num_envs
     learner = DevicePPO(obs_dim, act_dim, actor_lr=args.actor_lr, critic_lr=args.critic_lr, clip=args.clip, ent_coef=args.ent_coef,
-                        max_batch=max(1, rows // args.minibatches), max_rollout=rows, device=args.device)
+                        max_batch=max(1, rows // args.minibatches), max_rollout=rows, device=args.device,
+                        max_grad_norm=args.max_grad_norm, clip_value=args.clip_value, target_kl=args.target_kl, kl_control=args.kl_control)
     monitor = EpisodeMonitor(args.num_envs, device=args.device) if args.log_episodes else None
     first, logged = 1, 0                                        # logged: the episodes the previous evaluation line has covered
     if args.resume:
@@ -112,7 +122,9 @@ def main():
             print("iter %d: %.0f control steps/s, %.0f updates/s, reward/step %.4f, value loss %.4f, policy loss %.4f, approx_kl %.5f, "
                   "clip_frac %.3f, eval return %.3f"
                   % (it, (it - first + 1) * args.steps / dt, (it - first + 1) * args.epochs * args.minibatches / dt,
-                     rec["reward"].mean().item(), last[0], last[1], last[2], last[3], ret.mean().item()))
+                     rec["reward"].mean().item(), last[0], last[1], last[2], last[3], ret.mean().item())
+                  + (", lr_scale %.4f, applied updates %d" % (learner.control_state()["lr_scale"], learner.control_state()["actor_steps"])
+                     if learner.controlled else ""))
             if monitor is not None:
                 log = monitor.summary(since=logged)
                 logged = int(monitor.count.item())

@@ -80,6 +80,47 @@ int etg_ppo_learn_rows(EtgPpo* h, const float* obs, const float* eps, const long
 int etg_ppo_grads(EtgPpo* h, const float* obs, const float* head_old, const float* eps, const float* logp_old, const float* adv,
                   const float* ret, int n, float* const* grads, void* stream);
 
+/* ---- Controls: gradient-norm clipping, value clipping and a KL rule, all off (0) by default.  With all three off every entry
+ * point above enqueues the launches and gives the bits it gave before these existed.  With one on, an update's clip coefficient,
+ * its learning-rate scale and whether it is applied at all are decided ON THE DEVICE, from device memory, so an update still
+ * enqueues plain launches, waits for nothing and gives the same bits from the same inputs.  (The entry points of this part carry
+ * a 2 in their names: the 15 above are the base list, which stays as it is.)
+ *
+ *   max_grad_norm  per optimizer (the actor's 8 tensors, then the critics' 12): sq = the sum of squares of the group's gradients
+ *                  accumulated in double in a fixed order, norm = (float) sqrt(sq), coef = min(1, max_grad_norm / (norm + 1e-6)) in
+ *                  fp32, every gradient * coef, rounded once, before Adam            (torch.nn.utils.clip_grad_norm_)
+ *   clip_value     PPO2's clipped value loss against v_old, the value at collection time.  Per critic i: d = Q_i - v_old,
+ *                  inside = |d| <= c, vclip = v_old + clamp(d, -c, c), e1 = (Q_i - ret)^2, e2 = (vclip - ret)^2; the row's loss is e1
+ *                  with dQ_i = 2 (Q_i - ret) / n where inside or e1 >= e2, otherwise e2, a constant of the row, with dQ_i = 0.
+ *                  stats4[0] is the mean of the chosen terms, summed over the critics
+ *   target_kl      judged between the actor's backward pass and its Adam step on kl = this update's approx_kl, summed as stats4[2] is:
+ *                    ETG_PPO_KL_STOP      kl > 1.5 target_kl sets the stop flag.  While it is set an update still evaluates its
+ *                                         losses and stats, but parameters, moments and step counts of both optimizers stay
+ *                                         as they are.  etg_ppo2_reset_stop clears it
+ *                    ETG_PPO_KL_ADAPTIVE  kl > 2 target_kl: lr_scale /= 1.5; else 0 < kl < target_kl / 2: lr_scale *= 1.5; then
+ *                                         lr_scale is clamped so that actor_lr * lr_scale lies in [lr_lo, lr_hi].  Both optimizers
+ *                                         step with lr * lr_scale (a double; the product in double), from this update on
+ * Errors, beside the ones above: ETG_ERR_BAD_ARG for a negative or non-finite setting, lr_lo > lr_hi, an unknown mode (all three
+ * checked before the handle), and for an update with value clipping on and no v_old.                                              */
+#define ETG_PPO_KL_STOP 0
+#define ETG_PPO_KL_ADAPTIVE 1
+
+/* may be called between updates, like etg_ppo_set_hyper */
+int etg_ppo2_set_controls(EtgPpo* h, double max_grad_norm, double clip_value, double target_kl, int kl_mode, double lr_lo, double lr_hi);
+/* etg_ppo_learn / etg_ppo_grads with v_old [n] (may be NULL while value clipping is off).  etg_ppo_learn_rows needs no variant:
+ * it reads the handle's v, which etg_ppo_prepare wrote, through idx.  The gradients of etg_ppo2_grads are the unclipped ones */
+int etg_ppo2_learn(EtgPpo* h, const float* obs, const float* head_old, const float* eps, const float* logp_old, const float* adv,
+                   const float* ret, const float* v_old, int n, float* stats4, void* stream);
+int etg_ppo2_grads(EtgPpo* h, const float* obs, const float* head_old, const float* eps, const float* logp_old, const float* adv,
+                   const float* ret, const float* v_old, int n, float* const* grads, void* stream);
+/* clears the stop flag: enqueued, nothing waits */
+int etg_ppo2_reset_stop(EtgPpo* h, void* stream);
+/* the control state.  set: lr_scale (> 0) and the stop flag, enqueued.  get WAITS for the stream, then reads into HOST memory (a
+ * NULL pointer skips that part): lr_scale, the stop flag, steps2 = both optimizers' step counts, grad_norms2 = the actor's and
+ * the critics' gradient norm of the last applied update with gradient clipping on (0 before the first) */
+int etg_ppo2_set_state(EtgPpo* h, double lr_scale, int stopped, void* stream);
+int etg_ppo2_get_state(EtgPpo* h, double* lr_scale, int* stopped, long long* steps2, double* grad_norms2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

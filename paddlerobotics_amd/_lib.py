@@ -48,6 +48,9 @@ HEIGHTSCAN_SYMBOLS = ["etg_scan_pose", "etg_height_scan_at", "etg_height_scan"]
 PPO_SYMBOLS = ["etg_ppo_create", "etg_ppo_destroy", "etg_ppo_set_hyper", "etg_ppo_load", "etg_ppo_store", "etg_ppo_load_opt",
                "etg_ppo_store_opt", "etg_ppo_sync_policy", "etg_ppo_prepare", "etg_ppo_gae", "etg_ppo_norm_adv", "etg_ppo_fetch",
                "etg_ppo_learn", "etg_ppo_learn_rows", "etg_ppo_grads"]
+# ... and its controls (the same header, "Controls"): a list of their own, the base list above stays as it is
+PPO_CONTROL_SYMBOLS = ["etg_ppo2_set_controls", "etg_ppo2_learn", "etg_ppo2_grads", "etg_ppo2_reset_stop", "etg_ppo2_set_state",
+                       "etg_ppo2_get_state"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 
@@ -171,6 +174,12 @@ def load():
     lib.etg_ppo_learn.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
     lib.etg_ppo_learn_rows.argtypes = [vp, vp, vp, vp, i32, vp, vp]
     lib.etg_ppo_grads.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp), vp]
+    lib.etg_ppo2_set_controls.argtypes = [vp, C.c_double, C.c_double, C.c_double, i32, C.c_double, C.c_double]
+    lib.etg_ppo2_learn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+    lib.etg_ppo2_grads.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp), vp]
+    lib.etg_ppo2_reset_stop.argtypes = [vp, vp]
+    lib.etg_ppo2_set_state.argtypes = [vp, C.c_double, i32, vp]
+    lib.etg_ppo2_get_state.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_longlong), C.POINTER(C.c_double), vp]
     lib.etg_rollout_actions.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.etg_prepare_next_dynamics.argtypes = [vp, vp, vp, vp]
     lib.etg_next_dynamics_pending.argtypes = [vp, vp, vp]

@@ -205,5 +205,142 @@ static __global__ void __launch_bounds__(256) k_ppo_stats(int n, int B, const fl
   }
 }
 
+// ------------------------------------------------------------------------------------------------- the update's controls
+// Gradient-norm clipping, value clipping and the KL rule (include/etgsim_ppo.h "Controls").  What they decide -- the clip
+// coefficient, the learning-rate scale, whether the update is applied -- is decided on the device from device memory:
+//   ctl[0] = lr_scale, ctl[1] / ctl[2] = the gradient norm of the actor's / the critics' last applied step (doubles)
+//   flag[0] = 1 while the updates are stopped (int)
+constexpr int NORM_BLOCKS = 64;   // workgroups of the squared-norm reduction: part[NORM_BLOCKS] doubles per region
+
+// Sum of squares of a flat region of G, first stage: workgroup g sums, in double, the float4s g * 256 + t + k * 256 * NORM_BLOCKS,
+// workgroup 0's first lanes add the region's tail (n & 3 floats), the workgroup's 256 sums are added in the LDS tree's fixed order
+// and part[g] gets the result.  No atomics: the second stage (k_adam_ctl) adds the NORM_BLOCKS partials in a fixed order.
+static __global__ void __launch_bounds__(256) k_sqnorm(const float* __restrict__ G, long n, double* __restrict__ part) {
+  __shared__ double sm[256];
+  const int t = threadIdx.x;
+  const long n4 = n >> 2;
+  double s = 0.0;
+  for (long i = (long)blockIdx.x * 256 + t; i < n4; i += 256L * NORM_BLOCKS) {
+    const float4 g = ((const float4*)G)[i];
+    s += (double)g.x * (double)g.x; s += (double)g.y * (double)g.y; s += (double)g.z * (double)g.z; s += (double)g.w * (double)g.w;
+  }
+  if (blockIdx.x == 0 && (n4 << 2) + t < n) {
+    const double x = (double)G[(n4 << 2) + t];
+    s += x * x;
+  }
+  sm[t] = s;
+  for (int w = 128; w > 0; w >>= 1) {
+    __syncthreads();
+    if (t < w) sm[t] += sm[t + w];
+  }
+  if (t == 0) part[blockIdx.x] = sm[0];
+}
+
+// The controller, one workgroup, between the actor's backward pass and its Adam step.  kl = mean(rows_kl) is summed exactly as
+// k_ppo_stats sums it (lane t takes rows t, t + 256, ..; the same tree; / (float) n), so the number judged is the number reported.
+//   mode 0 (stop):      kl > 1.5 target sets flag[0]
+//   mode 1 (adaptive):  kl > 2 target: scale /= 1.5;  else 0 < kl < target / 2: scale *= 1.5;  then scale into [smin, smax]
+// (target <= 0: no rule).  With the flag clear afterwards, both optimizers' step counts and bias corrections are bumped: this
+// update will be applied.  With it set nothing is counted, and k_adam_ctl writes nothing.
+static __global__ void __launch_bounds__(256) k_ppo_ctl(int n, const float* __restrict__ rows_kl, double target, int mode, double smin,
+                                                        double smax, double* __restrict__ ctl, int* __restrict__ flag,
+                                                        long long* __restrict__ steps, double* __restrict__ bc) {
+  __shared__ float sm[256];
+  const int t = threadIdx.x;
+  float s = 0.0f;
+  for (int b = t; b < n; b += 256) s += rows_kl[b];
+  sm[t] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) sm[t] += sm[t + w];
+    __syncthreads();
+  }
+  if (t != 0) return;
+  const double kl = (double)(sm[0] / (float)n);
+  int stopped = flag[0];
+  if (target > 0.0 && !stopped) {
+    if (mode == 0) {
+      if (kl > 1.5 * target) { stopped = 1; flag[0] = 1; }
+    } else {
+      double scale = ctl[0];
+      if (kl > 2.0 * target) scale /= 1.5;
+      else if (kl > 0.0 && kl < target / 2.0) scale *= 1.5;
+      ctl[0] = fmin(fmax(scale, smin), smax);
+    }
+  }
+  if (!stopped) { bump_step(steps, bc); bump_step(steps + 1, bc + 2); }
+}
+
+// k_adam (sac_core.h) without a target, adam1 call for call, under the controls: nothing is written while flag[0] is set; the
+// gradient is g * coef, rounded once, with coef = min(1, max_norm / (norm + 1e-6)) in fp32 from norm = (float) sqrt(sum of the
+// NORM_BLOCKS partials of k_sqnorm), every workgroup adding them in the same tree (part == NULL: coef = 1); the step is
+// -(float)((lr * lr_scale) / bc[0]) with the product formed in double.  coef == 1, lr_scale == 1 and a clear flag give k_adam's bits:
+// g * 1.0f is g and lr * 1.0 is lr.  Workgroup 0 leaves the norm in *norm_out.
+static __global__ void __launch_bounds__(256) k_adam_ctl(float* __restrict__ P, const float* __restrict__ G, float* __restrict__ M,
+                                                         float* __restrict__ V, long n, double lr, const double* __restrict__ bc,
+                                                         const double* __restrict__ part, float max_norm, const double* __restrict__ ctl,
+                                                         const int* __restrict__ flag, double* __restrict__ norm_out) {
+  __shared__ double sm[NORM_BLOCKS];
+  if (flag[0]) return;   // the same word for every lane of the launch: nobody is left at the barriers below
+  float coef = 1.0f;
+  if (part) {
+    const int t = threadIdx.x;
+    if (t < NORM_BLOCKS) sm[t] = part[t];
+    for (int w = NORM_BLOCKS / 2; w > 0; w >>= 1) {
+      __syncthreads();
+      if (t < w) sm[t] += sm[t + w];
+    }
+    __syncthreads();
+    const float norm = (float)sqrt(sm[0]);
+    coef = fminf(1.0f, __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f)));
+    if (blockIdx.x == 0 && t == 0) *norm_out = (double)norm;
+  }
+  const float nstep = -(float)((lr * ctl[0]) / bc[0]), bc2s = (float)bc[1];
+  const long n4 = n >> 2, stride = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    float4 p = ((float4*)P)[i], m = ((float4*)M)[i], v = ((float4*)V)[i];
+    const float4 g = ((const float4*)G)[i];
+    sac::adam1(p.x, __fmul_rn(g.x, coef), m.x, v.x, nstep, bc2s); sac::adam1(p.y, __fmul_rn(g.y, coef), m.y, v.y, nstep, bc2s);
+    sac::adam1(p.z, __fmul_rn(g.z, coef), m.z, v.z, nstep, bc2s); sac::adam1(p.w, __fmul_rn(g.w, coef), m.w, v.w, nstep, bc2s);
+    ((float4*)P)[i] = p; ((float4*)M)[i] = m; ((float4*)V)[i] = v;
+  }
+  const long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x;   // the region's tail (fewer than 4 floats)
+  if (i < n) {
+    float p = P[i], m = M[i], v = V[i];
+    sac::adam1(p, __fmul_rn(G[i], coef), m, v, nstep, bc2s);
+    P[i] = p; M[i] = m; V[i] = v;
+  }
+}
+
+// k_value_dq with PPO2's clipped value loss against v_old, the value at collection time (through idx when given), clip range c:
+//   d = q - v_old,  inside = |d| <= c,  vclip = v_old + clamp(d, -c, c),  e1 = (q - ret)^2,  e2 = (vclip - ret)^2
+// the row's loss is e1 with dq = 2 (q - ret) / n where inside or e1 >= e2; otherwise e2, a constant of the row, with dq = 0
+static __global__ void __launch_bounds__(256) k_value_dq_clip(int n, int B, const float* __restrict__ q, const float* __restrict__ ret,
+                                                              const float* __restrict__ v_old, const long long* __restrict__ idx,
+                                                              float c, float* __restrict__ dq, float* __restrict__ rows) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= n) return;
+  const long long r = idx ? idx[b] : (long long)b;
+  const float y = ret[r], vo = v_old[r];
+  const float s = 2.0f / (float)n;
+#pragma unroll
+  for (int z = 0; z < 2; z++) {
+    const float qi = q[z * B + b];
+    const float d = qi - vo, e = qi - y;
+    const float ec = (vo + fminf(fmaxf(d, -c), c)) - y;
+    const float e1 = e * e, e2 = ec * ec;
+    const bool first = fabsf(d) <= c || e1 >= e2;
+    dq[z * B + b] = first ? e * s : 0.0f;
+    rows[z * B + b] = first ? e1 : e2;
+  }
+}
+
+// the control state written from the host without a copy from its memory: which & 1 sets lr_scale, which & 2 the stop flag
+static __global__ void k_ctl_set(double* __restrict__ ctl, int* __restrict__ flag, int which, double scale, int stopped) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (which & 1) ctl[0] = scale;
+  if (which & 2) flag[0] = stopped;
+}
+
 }  // namespace ppo
 #endif  // PPO_CORE_H_

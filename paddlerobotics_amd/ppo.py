@@ -20,9 +20,19 @@ On a HIP device the work runs in csrc/ppo_learn.hip (include/etgsim_ppo.h); lear
 return, nothing waits for the host.  `fused=False` is the DEFINITION: the same arithmetic written with stock torch, autograd and
 torch.optim.Adam, on any torch device, fp32 or fp64; the kernels are tested against it.
 
-Left out: gradient-norm clipping, value clipping, a KL-adaptive learning rate or early stopping (the caller has approx_kl in the
-stats and set_hyper), and observations wider than 64 columns.
+Controls, all off by default (DESIGN.md "The PPO learner", include/etgsim_ppo.h "Controls"): max_grad_norm (clip_grad_norm_ per
+optimizer), clip_value (PPO2's clipped value loss against the value at collection time) and target_kl with kl_control = "stop"
+(stable-baselines3's early stopping) or "adaptive" (rsl_rl's learning-rate schedule).  On the fused path the gradient norm, the
+clip coefficient, the KL decision and the learning-rate scale live on the device: an update still waits for nothing.
+control_state() reads them back, and is the only call that waits.
+
+  clip_coefficient(grads, max_grad_norm) -> (coef, norm)                     the pure pieces of the controls' definition
+  value_clip_rows(q, v_old, ret, c) -> (row loss, first branch)
+  kl_controller(kl, target_kl, mode, scale, stopped, actor_lr, bounds) -> (scale, stopped)
+
+Left out: observations wider than 64 columns.
 """
+import ctypes as C
 import math
 import struct
 from collections import OrderedDict
@@ -102,21 +112,148 @@ def value(p, obs):
     return 0.5 * (q1 + q2)
 
 
+KL_MODES = ("stop", "adaptive")     # include/etgsim_ppo.h: ETG_PPO_KL_STOP, ETG_PPO_KL_ADAPTIVE
+
+
+def clip_coefficient(grads, max_grad_norm):
+    """(coef, norm) of one optimizer's gradients: sq = the sum of their squares accumulated in fp64, norm = sqrt(sq) rounded to the
+    gradients' dtype, coef = min(1, max_grad_norm / (norm + 1e-6)) in that dtype -- torch.nn.utils.clip_grad_norm_ with the
+    accumulation pinned.  Every gradient is then multiplied by coef (also when it is 1)."""
+    grads = list(grads)
+    sq = sum(((g.detach().double() ** 2).sum() for g in grads), torch.zeros((), dtype=torch.float64, device=grads[0].device))
+    norm = sq.sqrt().to(grads[0].dtype)
+    return torch.clamp(float(max_grad_norm) / (norm + 1e-6), max=1.0), norm
+
+
+def value_clip_rows(q, v_old, ret, c):
+    """PPO2's clipped value loss of one critic, row by row, written so that no tie is ambiguous: with d = q - v_old, inside = |d| <= c,
+    vclip = v_old + clamp(d, -c, c), e1 = (q - ret)^2, e2 = (vclip - ret)^2 the row's loss is e1 where inside or e1 >= e2 (the
+    gradient is 2 (q - ret)), and otherwise e2 as a CONSTANT of the row (no gradient).  In value this is max(e1, e2): inside,
+    vclip = q.  Returns (rows, first) with first = the rows on the e1 branch."""
+    d = q - v_old
+    e1 = (q - ret) ** 2
+    e2 = ((v_old + torch.clamp(d, min=-c, max=c)) - ret) ** 2
+    first = (d.abs() <= c) | (e1 >= e2)
+    return torch.where(first, e1, e2.detach()), first
+
+
+def kl_controller(kl, target_kl, mode, scale, stopped, actor_lr, bounds):
+    """The KL rule as a pure function of Python floats: (scale, stopped) after judging this update's approx_kl.
+    "stop" (stable-baselines3): kl > 1.5 target_kl sets stopped.  "adaptive" (rsl_rl): kl > 2 target_kl: scale /= 1.5; else
+    0 < kl < target_kl / 2: scale *= 1.5; then scale is clamped to [lo / actor_lr, hi / actor_lr].  Nothing is judged while
+    stopped, or without a target."""
+    if not target_kl or stopped:
+        return scale, stopped
+    if mode == "stop":
+        return scale, kl > 1.5 * target_kl
+    if kl > 2.0 * target_kl:
+        scale = scale / 1.5
+    elif 0.0 < kl < target_kl / 2.0:
+        scale = scale * 1.5
+    if actor_lr > 0.0:
+        scale = min(max(scale, bounds[0] / actor_lr), bounds[1] / actor_lr)
+    return scale, stopped
+
+
 class DevicePPO(ActorCriticLearner):
     """See the module's docstring.  max_batch: the most rows of one update; max_rollout: the most rows T * N of a rollout."""
     PREFIX = "ppo"
     HYPER = ("actor_lr", "critic_lr", "clip", "ent_coef")
 
     def __init__(self, obs_dim, action_dim=12, hidden=256, actor_lr=3e-4, critic_lr=3e-4, clip=0.2, ent_coef=0.0, norm_adv=True,
-                 max_batch=32768, max_rollout=131072, device="cuda:0", fused=None, dtype=torch.float32, seed=0):
+                 max_batch=32768, max_rollout=131072, device="cuda:0", fused=None, dtype=torch.float32, seed=0,
+                 max_grad_norm=None, clip_value=None, target_kl=None, kl_control="stop", kl_lr_bounds=(1e-5, 1e-2)):
         if int(obs_dim) < 1 or int(obs_dim) > MAX_OBS_DIM:
             raise ValueError("obs_dim = %d is outside 1..%d, the range of the learner's kernels" % (int(obs_dim), MAX_OBS_DIM))
         if int(max_batch) < 1 or int(max_rollout) < 1:
             raise ValueError("max_batch and max_rollout must be at least 1")
+        for name, x in (("max_grad_norm", max_grad_norm), ("clip_value", clip_value), ("target_kl", target_kl)):
+            if x is not None and not (math.isfinite(float(x)) and float(x) > 0.0):
+                raise ValueError("%s = %r: None (off) or a finite number > 0" % (name, x))
+        lo, hi = (float(x) for x in kl_lr_bounds)
+        if kl_control not in KL_MODES or not (math.isfinite(lo) and math.isfinite(hi) and 0.0 <= lo <= hi):
+            raise ValueError("kl_control is one of %s and kl_lr_bounds = (lo, hi) with 0 <= lo <= hi" % (KL_MODES,))
+        self.max_grad_norm, self.clip_value, self.target_kl = (None if x is None else float(x) for x in (max_grad_norm, clip_value, target_kl))
+        self.kl_control, self.kl_lr_bounds = kl_control, (lo, hi)
+        self.lr_scale, self._stopped, self._grad_norms = 1.0, False, [0.0, 0.0]      # the definition's control state
         self.actor_lr, self.critic_lr, self.clip, self.ent_coef = float(actor_lr), float(critic_lr), float(clip), float(ent_coef)
         self.norm_adv, self.max_rollout = bool(norm_adv), int(max_rollout)
         super().__init__((int(obs_dim), int(action_dim), int(hidden), int(max_batch), int(max_rollout)), obs_dim, action_dim, hidden,
                          max_batch, device, fused, dtype, seed)
+
+    # ---- the controls
+    @property
+    def controlled(self):
+        return self.max_grad_norm is not None or self.clip_value is not None or self.target_kl is not None
+
+    def _set_hyper(self):
+        super()._set_hyper()
+        self._check(self._lib.etg_ppo2_set_controls(self._h, self.max_grad_norm or 0.0, self.clip_value or 0.0, self.target_kl or 0.0,
+                                                    KL_MODES.index(self.kl_control), *self.kl_lr_bounds))
+
+    def reset_kl_stop(self):
+        """clears the stop flag that kl_control="stop" sets (learn_rollout does so before its first update); nothing waits"""
+        if self.fused:
+            self._check(self._lib.etg_ppo2_reset_stop(self._h, self._stream()))
+        else:
+            self._stopped = False
+
+    def control_state(self):
+        """{lr_scale, stopped, actor_steps, critic_steps, grad_norm_actor, grad_norm_critic}: the norms are those of the last applied
+        update with max_grad_norm on (0.0 before the first).  The one call of the controls that waits for the device."""
+        if self.fused:
+            scale, stopped, steps, norms = C.c_double(), C.c_int(), (C.c_longlong * 2)(), (C.c_double * 2)()
+            self._check(self._lib.etg_ppo2_get_state(self._h, C.byref(scale), C.byref(stopped), steps, norms, self._stream()))
+            scale, stopped, steps, norms = scale.value, bool(stopped.value), list(steps), list(norms)
+        else:
+            scale, stopped, steps, norms = self.lr_scale, self._stopped, super().optimizer_state()["steps"], self._grad_norms
+        return {"lr_scale": float(scale), "stopped": bool(stopped), "actor_steps": int(steps[0]), "critic_steps": int(steps[1]),
+                "grad_norm_actor": float(norms[0]), "grad_norm_critic": float(norms[1])}
+
+    def load_control_state(self, state):
+        """lr_scale and stopped of control_state() / optimizer_state()["control"]"""
+        scale, stopped = float(state["lr_scale"]), bool(state["stopped"])
+        if self.fused:
+            self._check(self._lib.etg_ppo2_set_state(self._h, scale, int(stopped), self._stream()))
+        else:
+            self.lr_scale, self._stopped = scale, stopped
+
+    def optimizer_state(self):
+        """ActorCriticLearner.optimizer_state() plus "control": {lr_scale, stopped}, so that a resumed run continues its schedule"""
+        out = super().optimizer_state()
+        cs = self.control_state()
+        out["control"] = {"lr_scale": cs["lr_scale"], "stopped": cs["stopped"]}
+        return out
+
+    def load_optimizer_state(self, state):
+        super().load_optimizer_state(state)
+        if "control" in state:
+            self.load_control_state(state["control"])
+
+    def _judge(self, kl):
+        """the definition's controller, between the actor's backward pass and its step: True when this update is applied"""
+        self.lr_scale, self._stopped = kl_controller(float(kl), self.target_kl, self.kl_control, self.lr_scale, self._stopped, self.actor_lr,
+                                                     self.kl_lr_bounds)
+        return not self._stopped
+
+    def _step(self, which):
+        """one optimizer's step under the controls: the gradients times the clip coefficient, the learning rate times lr_scale"""
+        opt, keys, lr = ((self._actor_opt, ACTOR_KEYS, self.actor_lr), (self._critic_opt, CRITIC_KEYS, self.critic_lr))[which]
+        if self.max_grad_norm is not None:
+            gs = [self.params[k].grad for k in keys]
+            coef, norm = clip_coefficient(gs, self.max_grad_norm)
+            for g in gs:
+                g.mul_(coef)
+            self._grad_norms[which] = norm
+        opt.param_groups[0]["lr"] = lr * self.lr_scale
+        opt.step()
+
+    def _v_old(self, v_old, n):
+        if self.clip_value is None:
+            return None
+        if v_old is None:
+            raise ValueError("clip_value is on: pass v_old [n], the value of every row at collection time (prepare()'s v)")
+        return self._vec(v_old, n)
 
     # ---- checks (the same on both paths, so that the definition refuses what the kernels refuse)
     def _check_n(self, n, what="batch"):
@@ -158,22 +295,43 @@ class DevicePPO(ActorCriticLearner):
     def _actor_loss(self, obs, head_old, eps, logp_old, adv):
         return self._actor_terms(obs, head_old, eps, logp_old, adv)[0]
 
-    def _value_loss(self, obs, ret):
+    def _value_loss(self, obs, ret, v_old=None):
         q1, q2 = value_heads(self.params, obs)
-        return F.mse_loss(q1, ret) + F.mse_loss(q2, ret)
+        if self.clip_value is None:
+            return F.mse_loss(q1, ret) + F.mse_loss(q2, ret)
+        return value_clip_rows(q1, v_old, ret, self.clip_value)[0].mean() + value_clip_rows(q2, v_old, ret, self.clip_value)[0].mean()
 
     # ---- one update
-    def learn(self, obs, head_old, eps, logp_old, adv, ret):
+    def learn(self, obs, head_old, eps, logp_old, adv, ret, v_old=None):
         """one update on n rows: the actor's step on the clipped surrogate, then both critics' regression onto `ret` on [obs | 0].
-        head_old [n, 24] = (mean, raw log_std) of the actor that acted, eps [n, 12] its N(0,1) draws, logp_old, adv, ret [n].
-        Returns the stats [4] = STATS on the device."""
+        head_old [n, 24] = (mean, raw log_std) of the actor that acted, eps [n, 12] its N(0,1) draws, logp_old, adv, ret [n];
+        v_old [n], the rows' value at collection time, is read with clip_value on.  Returns the stats [4] = STATS on the device.
+        With kl_control="stop" an update honours and sets the stop flag (reset_kl_stop): a stopped update evaluates its stats only."""
         (obs, head_old, eps, logp_old, adv, ret), n = self._batch(obs, head_old, eps, logp_old, adv, ret)
+        v_old = self._v_old(v_old, n)
         self._policy_stale = True
         if self.fused:
             stats = torch.empty(4, device=self.device)
+            if v_old is not None:
+                self._check(self._lib.etg_ppo2_learn(self._h, _ptr(obs), _ptr(head_old), _ptr(eps), _ptr(logp_old), _ptr(adv), _ptr(ret),
+                                                     _ptr(v_old), n, _ptr(stats), self._stream()))
+                return stats
             self._check(self._lib.etg_ppo_learn(self._h, _ptr(obs), _ptr(head_old), _ptr(eps), _ptr(logp_old), _ptr(adv), _ptr(ret), n,
                                                 _ptr(stats), self._stream()))
             return stats
+        if self.controlled:
+            aloss, kl, clip_frac, _ = self._actor_terms(obs, head_old, eps, logp_old, adv)
+            self._actor_opt.zero_grad()
+            aloss.backward()
+            apply = self._judge(kl)
+            if apply:
+                self._step(0)
+            vloss = self._value_loss(obs, ret, v_old)
+            self._critic_opt.zero_grad()
+            vloss.backward()
+            if apply:
+                self._step(1)
+            return torch.stack([vloss.detach(), aloss.detach(), kl, clip_frac])
         aloss, kl, clip_frac, _ = self._actor_terms(obs, head_old, eps, logp_old, adv)
         self._actor_opt.zero_grad()
         aloss.backward()
@@ -184,16 +342,21 @@ class DevicePPO(ActorCriticLearner):
         self._critic_opt.step()
         return torch.stack([vloss.detach(), aloss.detach(), kl, clip_frac])
 
-    def grads(self, obs, head_old, eps, logp_old, adv, ret):
-        """the 20 gradients of the update learn() would apply; nothing changes"""
+    def grads(self, obs, head_old, eps, logp_old, adv, ret, v_old=None):
+        """the 20 gradients of the losses of the update learn() would make, before any gradient clipping; nothing changes"""
         (obs, head_old, eps, logp_old, adv, ret), n = self._batch(obs, head_old, eps, logp_old, adv, ret)
+        v_old = self._v_old(v_old, n)
         if self.fused:
             gs = self._empty_like_params()
+            if v_old is not None:
+                self._check(self._lib.etg_ppo2_grads(self._h, _ptr(obs), _ptr(head_old), _ptr(eps), _ptr(logp_old), _ptr(adv), _ptr(ret),
+                                                     _ptr(v_old), n, self._ptrs(gs), self._stream()))
+                return OrderedDict(zip(KEYS, gs))
             self._check(self._lib.etg_ppo_grads(self._h, _ptr(obs), _ptr(head_old), _ptr(eps), _ptr(logp_old), _ptr(adv), _ptr(ret), n,
                                                 self._ptrs(gs), self._stream()))
             return OrderedDict(zip(KEYS, gs))
         ga = torch.autograd.grad(self._actor_loss(obs, head_old, eps, logp_old, adv), [self.params[k] for k in ACTOR_KEYS])
-        gc = torch.autograd.grad(self._value_loss(obs, ret), [self.params[k] for k in CRITIC_KEYS])
+        gc = torch.autograd.grad(self._value_loss(obs, ret, v_old), [self.params[k] for k in CRITIC_KEYS])
         return OrderedDict(zip(KEYS, list(ga) + list(gc)))
 
     # ---- the rollout
@@ -270,6 +433,8 @@ class DevicePPO(ActorCriticLearner):
             self._check(self._lib.etg_ppo_gae(self._h, _ptr(reward), _ptr(terminal), _ptr(done8), T, N, g, gl, None, None, None, None, s))
             if self.norm_adv:
                 self._check(self._lib.etg_ppo_norm_adv(self._h, None, n, s))
+            if self.controlled:
+                self.reset_kl_stop()
             for e in range(E):
                 idx = torch.randperm(n, device=self.device, generator=generator)[:M * B].view(M, B)
                 for k in range(M):
@@ -280,11 +445,14 @@ class DevicePPO(ActorCriticLearner):
         adv, ret = adv.reshape(n), ret.reshape(n)
         if self.norm_adv:
             adv = normalise(adv)
+        if self.controlled:
+            self.reset_kl_stop()
         for e in range(E):
             idx = torch.randperm(n, device=self.device, generator=generator)[:M * B].view(M, B)
             for k in range(M):
                 i = idx[k]
-                stats[e * M + k] = self.learn(obs[i], head_old[i], eps[i], logp_old[i], adv[i], ret[i])
+                stats[e * M + k] = self.learn(obs[i], head_old[i], eps[i], logp_old[i], adv[i], ret[i],
+                                              v[i] if self.clip_value is not None else None)
         return stats
 
 
