@@ -148,12 +148,14 @@ class OracleEnsemble:
 
     def step(self, action, donef=None, want_info=True):
         a32 = np.asarray(action, dtype=np.float32)           # what the GPU receives
-        self._obs = [np.asarray(self.o32.step(a32, donef, want_info=False)[0], dtype=np.float64)]
+        outs = [self.o32.step(a32, donef, want_info=False)]
         for o in self.nudged:
-            self._obs.append(np.asarray(o.step(self._nudge(a32), donef, want_info=False)[0], dtype=np.float64))
+            outs.append(o.step(self._nudge(a32), donef, want_info=False))
         for o in self.res_members:
-            self._obs.append(np.asarray(o.step(a32.astype(np.float64), donef, want_info=False)[0], dtype=np.float64))
+            outs.append(o.step(a32.astype(np.float64), donef, want_info=False))
+        self._obs = [np.asarray(x[0], dtype=np.float64) for x in outs]
         out = self.nominal.step(a32.astype(np.float64), donef, want_info=want_info)
+        self.member_done = [np.asarray(x[2]).astype(bool) for x in outs]      # the members' own done flags of this step
         self._obs0 = np.asarray(out[0], dtype=np.float64)
         return out
 
