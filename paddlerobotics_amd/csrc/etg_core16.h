@@ -477,10 +477,10 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
   // row_newbcast and applied by every lane.
   // Under the residual stopping rule a robot that has converged is FROZEN for the sweeps the other robots of its wave still
   // need, so its result does not depend on its wave neighbours (batch invariance) and equals the oracle's, which stops per
-  // robot.  The default does it lazily (sweep_and_test below: sweep on, then put the values at convergence back); the sweeps
-  // still read their per-lane constants through `iAe`, `c0e`, `mue` for the ETG_EAGER_FREEZE build variant, which zeroes them
-  // instead (iAe = c0e = 0: every candidate equals the current impulse; mue = 1e30: the cone projection is the identity).
-  F iAe = iA, c0e = tgt * iA, mue = tp.mu;
+  // robot.  It is done lazily (sweep_and_test below: sweep on, then put the values at convergence back).  The eager form of
+  // round 3, which zeroed a converged robot's per-lane constants before the next sweep, lost the A/B comparison
+  // (profiles/r04_ab_experiments.txt); it is in the history.
+  const F c0 = tgt * iA;
   const F tangf = f1 + f2;
   // owner masks of the three rows of every leg, hoisted out of the sweeps (1 on the lane that owns row e of leg lp)
   F mk0[4], mt[4], mk3[4];
@@ -677,7 +677,10 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
   // and with / without the joint rows.
   auto solve = [&](auto pyramid_tag) {
     constexpr bool pyramid = decltype(pyramid_tag)::value;
-    F iAqe = iAq, c0qe = c0q;
+    // (the joint rows' constants under names of this lambda's own, first thing in it: a lambda lays its captures out in the order
+    // of their first use, and every kernel with body rows changes its instruction order when these two move down to
+    // joint_phase -- profiles/dead_paths_isa_identity.txt)
+    const F iAqs = iAq, c0qs = c0q;
     // the second rows' columns as the sweeps use them -- Bn: second row x the 8 normal rows (feet, then body); Bt: x the feet's
     // friction rows (t1, t2 of leg 0, ...); BBr / ATr: the body pairs' own -- and the second rows' velocity under the impulses
     // the sweeps start from (warm-started foot normals; lam2 = 0)
@@ -746,7 +749,7 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
 #pragma unroll
           for (int k = 1; k < 6; k++) zz = zz + zj[k] * zl[k];
           const F uq = sgn * (qj - zz);
-          const F dq = me * fmaxf_(-lamq, c0qe - uq * iAqe);
+          const F dq = me * fmaxf_(-lamq, c0qs - uq * iAqs);
           lamq = lamq + dq;
           const F sd = -(sgn * dq);
 #pragma unroll
@@ -815,15 +818,15 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
         // as the C++ below; the friction skip is folded into the per-lane constants of the friction phase
         if constexpr (body) {
           F lnq, lbn;
-          c.pgs_normals_body2(lam, u, u2, iAe, c0e, A, Ak, mk0, mk3, Bn, lnq, lbn);
+          c.pgs_normals_body2(lam, u, u2, iA, c0, A, Ak, mk0, mk3, Bn, lnq, lbn);
           const auto grip = lnq > zero;
-          c.pgs_tangents_disc2(lam, u, u2, sel_(grip, iAe, zero), sel_(grip, mue * lnq, F(1e30f)), A, mt, Bt);
+          c.pgs_tangents_disc2(lam, u, u2, sel_(grip, iA, zero), sel_(grip, tp.mu * lnq, F(1e30f)), A, mt, Bt);
           body_friction(lbn);
         } else {
-          c.pgs_normals(lam, u, iAe, c0e, A, mk0);
+          c.pgs_normals(lam, u, iA, c0, A, mk0);
           const F lnq = c.qb(lam, 0);
           const auto grip = lnq > zero;
-          c.pgs_tangents_disc(lam, u, sel_(grip, iAe, zero), sel_(grip, mue * lnq, F(1e30f)), A, mt);
+          c.pgs_tangents_disc(lam, u, sel_(grip, iA, zero), sel_(grip, tp.mu * lnq, F(1e30f)), A, mt);
         }
         return;
       }
@@ -831,7 +834,7 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
       // between the candidate and its broadcast, where the DPP read needs two wait states anyway
 #pragma unroll
       for (int lp = 0; lp < 4; lp++) {
-        F dln = fmaxf_(-lam, c0e - u * iAe);                          // = max(0, lam + c0 - u / A) - lam
+        F dln = fmaxf_(-lam, c0 - u * iA);                            // = max(0, lam + c0 - u / A) - lam
         lam = lam + mk0[lp] * dln;
         const F b = c.rbcast(dln, 4 * lp);
         u = u + A[lp][0] * b;
@@ -840,7 +843,7 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
       if (body) {   // the body normal rows: lk = max(0, lk - (u - tgt)/A)
 #pragma unroll
         for (int lp = 0; lp < 4; lp++) {
-          F dlk = fmaxf_(-lam, c0e - u * iAe);
+          F dlk = fmaxf_(-lam, c0 - u * iA);
           lam = lam + mk3[lp] * dlk;
           F bk = c.rbcast(dlk, 4 * lp + 3);
           u = u + Ak[lp] * bk;
@@ -852,11 +855,11 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
       // resolveConeFrictionConstraintRows; friction_model 1: each clamped on its own), and the two total changes are
       // broadcast once.  A foot whose normal impulse is not positive keeps its friction impulses (`if (totalImpulse > 0)`).
       const F lnq = c.qb(lam, 0);
-      const F lim = mue * lnq;
+      const F lim = tp.mu * lnq;
       const auto grip = lnq > zero;
 #pragma unroll
       for (int lp = 0; lp < 4; lp++) {
-        const F lc = lam - u * iAe;                                   // this lane's candidate (meaningful on the tangent lanes)
+        const F lc = lam - u * iA;                                    // this lane's candidate (meaningful on the tangent lanes)
         F dl;
         if (pyramid) {
           dl = fminf_(fmaxf_(lc, -lim), lim) - lam;
@@ -882,7 +885,7 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
         c.opaque(tol); c.opaque(tol2);
         const unsigned cap = (unsigned)(K.iters > 1 ? K.iters : 1) - 1u;
         unsigned rem = cap;
-        run_sweep_stream_(c, lam, u, u2, lam2, rem, iAe, c0e, mue, A, Ak, mk0, mk3, mt, Bn, Bt, iA2, K.body_mu, ATr, BBr, tol, tol2);
+        run_sweep_stream_(c, lam, u, u2, lam2, rem, iA, c0, tp.mu, A, Ak, mk0, mk3, mt, Bn, Bt, iA2, K.body_mu, ATr, BBr, tol, tol2);
         L.sweeps += (int)(cap - rem) + (rem != ~0u ? 1 : 0);      // (rem wraps on the sweep that reaches the cap)
         return;
       }
@@ -892,7 +895,7 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
       // ((lam - lam at the start of the sweep) * A_rr)^2 is <= the threshold, K.iters sweeps at most.
       // ((lam - lam0) A_rr)^2 > thr  <=>  |lam - lam0| > sqrt(thr) / A_rr: one subtraction and one compare per lane and sweep
       // against a tolerance made once per tick (inactive rows: iA = 0, no change, 0 > 0 is false); "any row of my robot"
-      // comes from the compare's wave mask (robot_any), not from a 4-stage lane reduction
+      // comes from the compare's wave mask (vote_robot), not from a 4-stage lane reduction
       // (the votes are taken compare by compare and OR-ed as wave masks: a vote on `a || b` goes through a 0/1 register and a
       // second compare -- three issue slots per sweep)
       F tol = F(K.res_sqrt) * iA, tol2 = F(K.res_sqrt) * iA2;
@@ -902,51 +905,32 @@ ETG_HD void physics_tick16(const Ctx& c, const KCfg& K, const TickPar<F>& tp, St
       bool more;
       auto frozen = lam < lam;                                        // (all false) robots that have converged
       auto sweep_and_test = [&]() {
-#ifdef ETG_EAGER_FREEZE   // A/B build variant: the round-3 form (constants zeroed before the next sweep)
-        constexpr bool lazy = false;
-#else
-        constexpr bool lazy = true;
-#endif
-        if constexpr (lazy) {
-          // A converged robot is frozen LAZILY: it sweeps on with its real constants and is put back to its values at
-          // convergence afterwards (two selects, three with joint rows) -- the same result bit for bit as zeroed constants,
-          // but the per-robot mask (ballot -> shift -> and -> compare: a 6-deep chain) is only needed AFTER the next sweep,
-          // so it leaves the sweep's critical path; the wave's exit test is the compare's wave mask alone.
-          const F lam0 = lam, u0 = u, lamq0 = lamq, lam20 = lam2, u20 = u2;
-          pgs_sweep();
-          it++;
-          lam = sel_(frozen, lam0, lam);
-          u = sel_(frozen, u0, u);
-          if (joints) lamq = sel_(frozen, lamq0, lamq);
-          auto moved = c.vote(fabsf_(lam - lam0) > tol);
-          if (joints) moved = c.vote_or(moved, c.vote(fabsf_(lamq - lamq0) > tolq));
-          if (body) {   // the second rows (inactive rows: iA2 = 0, no change, 0 > 0 is false)
-            lam2 = sel_(frozen, lam20, lam2);
-            u2 = sel_(frozen, u20, u2);
-            moved = c.vote_or(moved, c.vote(fabsf_(lam2 - lam20) > tol2));
-          }
-          if constexpr (body) {
-            more = c.vote_wave(moved);
-            if (more) { c.fence(); more = it < K.iters; }               // two scalar branches (merged into one condition the two tests
-                                                                        // go through lane masks: 7 scalar instructions instead of 4;
-                                                                        // the toe-spheres tick's unrolled exits lose 1 % with it)
-          } else {
-            more = c.vote_wave(moved) && it < K.iters;
-          }
-          frozen = !c.vote_robot(moved);
-          return;
-        }
-        static_assert(!body || lazy, "the eager-freeze A/B variant predates the body friction rows");
-        const F lam0 = lam, lamq0 = lamq;
+        // A converged robot is frozen LAZILY: it sweeps on with its real constants and is put back to its values at
+        // convergence afterwards (two selects, three with joint rows) -- the same result bit for bit as zeroed constants,
+        // but the per-robot mask (ballot -> shift -> and -> compare: a 6-deep chain) is only needed AFTER the next sweep,
+        // so it leaves the sweep's critical path; the wave's exit test is the compare's wave mask alone.
+        const F lam0 = lam, u0 = u, lamq0 = lamq, lam20 = lam2, u20 = u2;
         pgs_sweep();
         it++;
-        const auto live = joints ? c.robot_any((fabsf_(lam - lam0) > tol) || (fabsf_(lamq - lamq0) > tolq))
-                                 : c.robot_any(fabsf_(lam - lam0) > tol);
-        iAe = sel_(live, iAe, zero);
-        c0e = sel_(live, c0e, zero);
-        mue = sel_(live, mue, F(1e30f));
-        if (joints) { iAqe = sel_(live, iAqe, zero); c0qe = sel_(live, c0qe, zero); }
-        more = c.wave_any(live) && it < K.iters;
+        lam = sel_(frozen, lam0, lam);
+        u = sel_(frozen, u0, u);
+        if (joints) lamq = sel_(frozen, lamq0, lamq);
+        auto moved = c.vote(fabsf_(lam - lam0) > tol);
+        if (joints) moved = c.vote_or(moved, c.vote(fabsf_(lamq - lamq0) > tolq));
+        if (body) {   // the second rows (inactive rows: iA2 = 0, no change, 0 > 0 is false)
+          lam2 = sel_(frozen, lam20, lam2);
+          u2 = sel_(frozen, u20, u2);
+          moved = c.vote_or(moved, c.vote(fabsf_(lam2 - lam20) > tol2));
+        }
+        if constexpr (body) {
+          more = c.vote_wave(moved);
+          if (more) { c.fence(); more = it < K.iters; }               // two scalar branches (merged into one condition the two tests
+                                                                      // go through lane masks: 7 scalar instructions instead of 4;
+                                                                      // the toe-spheres tick's unrolled exits lose 1 % with it)
+        } else {
+          more = c.vote_wave(moved) && it < K.iters;
+        }
+        frozen = !c.vote_robot(moved);
       };
       if (Ctx::kPlain && !joints && !body) {
         // The default robot layer: the first 8 sweeps as nested forward exits (falling through costs nothing, the one taken

@@ -607,10 +607,6 @@ struct GpuCtx16 {
   __device__ __forceinline__ bool any(bool b) const { return __builtin_amdgcn_ballot_w64(b) != 0ull; }
   // the wave-uniform tests of the body paths work on the wave mask of a compare: "any lane", "any lane of leg lp (in any robot
   // of the wave)" are one scalar AND against a constant each
-#ifdef ETG_FORCE_BODY   // A/B build variant: every tick takes the body-row paths (what the emulation's force_body knob does)
-  __device__ __forceinline__ bool any_body(bool) const { return true; }
-  __device__ __forceinline__ unsigned body_mask(bool) const { return ~0u; }
-#else
   __device__ __forceinline__ bool any_body(bool b) const { return __builtin_amdgcn_ballot_w64(b) != 0ull; }
   // the wave mask folded to 32 bits (a leg's four lanes sit at the same bits of both halves): a leg's test is ONE s_and_b32
   // against a 32-bit literal that sets SCC (a 64-bit mask needs two ANDs and a compare)
@@ -618,20 +614,17 @@ struct GpuCtx16 {
     const unsigned long long m = __builtin_amdgcn_ballot_w64(b);
     return (unsigned)m | (unsigned)(m >> 32);
   }
-#endif
   __device__ __forceinline__ bool mask_any(unsigned m) const { return m != 0u; }
   __device__ __forceinline__ bool mask_leg(unsigned m, int lp) const { return (m & (0x000F000Fu << (4 * lp))) != 0u; }
   __device__ __forceinline__ unsigned uniform_bits(unsigned v) const { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }   // a wave-uniform value, kept in an SGPR
-  // (the builtin on the i1 itself: HIP's __any / __ballot take an int, and the compare's wave mask went through a
-  // v_cndmask 0/1 + v_cmp_ne + a wait state on its way in -- three issue slots per sweep)
-  __device__ __forceinline__ bool wave_any(bool b) const { return __builtin_amdgcn_ballot_w64(b) != 0ull; }   // "does any robot of the wave need another sweep?"
   // "does any lane of MY robot (16-lane row) see b?" from the wave mask of the compare
   __device__ __forceinline__ bool vote_robot(unsigned long long m) const {
     const unsigned f = (tid & 16) ? 0xFFFF0000u : 0x0000FFFFu;
     return ((tid & 32) ? ((unsigned)(m >> 32) & f) : ((unsigned)m & f)) != 0u;
   }
-  __device__ __forceinline__ bool robot_any(bool b) const { return vote_robot(__builtin_amdgcn_ballot_w64(b)); }
   // the residual rule's votes (etg_core16.h: sweep_and_test): one wave mask per compare, OR-ed as scalars
+  // (the builtin on the i1 itself: HIP's __any / __ballot take an int, and the compare's wave mask went through a
+  // v_cndmask 0/1 + v_cmp_ne + a wait state on its way in -- three issue slots per sweep)
   __device__ __forceinline__ unsigned long long vote(bool b) const { return __builtin_amdgcn_ballot_w64(b); }
   __device__ __forceinline__ unsigned long long vote_or(unsigned long long a, unsigned long long b) const { return a | b; }
   __device__ __forceinline__ bool vote_wave(unsigned long long m) const { return m != 0ull; }
@@ -911,7 +904,7 @@ struct GpuCtx16 {
     switch (lp) { case 0: ETG_PAIRB(1, 2); break; case 1: ETG_PAIRB(5, 6); break; case 2: ETG_PAIRB(9, 10); break; default: ETG_PAIRB(13, 14); break; }
 #undef ETG_PAIRB
   }
-#if !defined(ETG_SWEEP_BOOKKEEPING_OUTSIDE) && !defined(ETG_NO_ASM_SWEEP) && !defined(ETG_EAGER_FREEZE)
+#ifndef ETG_NO_ASM_SWEEP
   // ---- the residual-rule loop of a tick with body rows as ONE scheduled stream (etg_core16.h: solve; kSweepStream): the rows of
   // pgs_normals_body2, pgs_tangents_disc2 and pgs_pair_body, instruction for instruction, with everything sweep_and_test does
   // AROUND them -- copies, grip selects, the body pairs' constants and leg tests, the residual votes, the lazy freeze, the
@@ -941,11 +934,7 @@ struct GpuCtx16 {
     float w, wu, wu2, w2, t, dA, dB, lnq, lbn, iAg, limg, lim, lc, sq, sc, iA2g, lim2g, rr;
     unsigned x, gm, tmp;
     unsigned long long live, mv, sa;
-#ifdef ETG_FORCE_BODY
-#define ETG_SGM "s_or_b32 %[gm], -1, -1\n"
-#else
 #define ETG_SGM "s_or_b32 %[gm], vcc_lo, vcc_hi\n"            /* a leg's lanes at the same bits of both halves; SCC = any  */
-#endif
 #define ETG_SU2(D, LP, BOP) "v_fmac_f32_dpp %[wu2], %[" D "], %[" BOP "] row_newbcast:" #LP ETG_DPPC
 #define ETG_SROW(D, LP, AOP, MOP, FILL)                                              \
     "v_fma_f32 %[t], -%[wu], %[iA], %[c0]\n"                                         \
@@ -1119,13 +1108,11 @@ struct GpuCtx16 {
   // phase boundary of the 16-lane tick: no scheduling barrier in the product build.  A barrier here makes the tail of one
   // phase's dependent chain (the LDL^T solve, a DPP reduction) sit out its latency before the next phase may start; without
   // it the scheduler overlaps the two, registers and scratch stay where they were, and the headline rollout runs 3-6 %
-  // faster (profiles/r07_ab_experiments.txt section 5).  -DETG_PHASE_BARRIER16 restores the barriers for A/B builds; the
-  // profiling build keeps them around its s_memtime stamps so that every stamp closes exactly its own phase.
+  // faster (profiles/r07_ab_experiments.txt section 5).  The profiling build keeps them around its s_memtime stamps so
+  // that every stamp closes exactly its own phase.
   __device__ __forceinline__ void phase([[maybe_unused]] int id) const {
-#if defined(ETG_PHASE_BARRIER16) || defined(ETG_PROFILE_PHASES)
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 #ifdef ETG_PROFILE_PHASES
+    __builtin_amdgcn_sched_barrier(0);
     long long t = clock64();
     prof[id] += t - prof_last;
     prof_last = t;
@@ -1173,8 +1160,8 @@ template <bool FLAT, bool KNEE = false, bool PLAIN = false, bool SLOTB_LDS = fal
 #else
   static constexpr bool kGramMfma = true;
 #endif
-  // -DETG_SWEEP_BOOKKEEPING_OUTSIDE (A/B build variant): the round-7 form, sweep_and_test's own statements around the asm blocks
-#if defined(ETG_NO_ASM_SWEEP) || defined(ETG_SWEEP_BOOKKEEPING_OUTSIDE) || defined(ETG_EAGER_FREEZE)
+  // (the round-7 form, sweep_and_test's own statements around the asm blocks, measured against it: profiles/r08_ab_experiments.txt)
+#ifdef ETG_NO_ASM_SWEEP
   static constexpr bool kSweepStream = false;
 #else
   static constexpr bool kSweepStream = true;  // pgs_body_stream: the body tail's residual-rule loop, bookkeeping included
@@ -1398,16 +1385,11 @@ __global__ void __launch_bounds__(BLOCK) k_step16_ar(KCfg K, DevState D, const f
 template <bool FLAT, bool KNEE, bool PLAIN>
 __global__ void __launch_bounds__(BLOCK) k_rollout16(KCfg K, DevState D, int n_steps, float* obs, StatOut so) {
   __shared__ float lds_par[LDS16_FIELDS * BLOCK];
-#ifndef ETG_ROLLOUT16_STEP_LOCAL   // the default: rollout constants hoisted to the kernel's head, tick constants from HBM.  (A/B build
-  // variant -DETG_ROLLOUT16_STEP_LOCAL: formed anew every control step like the tape and closed-loop kernels -- 343 registers
-  // instead of 448 and 60 % fewer accumulator-register moves, and 0.4 % SLOWER on the same box: profiles/r06_ab_experiments.txt)
+  // rollout constants hoisted to the kernel's head, tick constants from HBM.  (Formed anew every control step like the tape and
+  // closed-loop kernels: 343 registers instead of 448 and 60 % fewer accumulator-register moves, and 0.4 % SLOWER on the same
+  // box: profiles/r06_ab_experiments.txt section 5)
   GpuCtx16T<FLAT, KNEE, PLAIN> c;
   if (!make_ctx16(K, D, c, lds_par)) return;
-#else
-  GpuCtx16W<FLAT, KNEE, PLAIN> c;
-  if (!make_ctx16_fields(K, D, c, lds_par, xcd_contiguous_block(), threadIdx.x)) return;
-  for (int k = 0; k < PR_N; k++) lds_par[k * 64 + threadIdx.x] = D.par[(size_t)k * c.NL + c.col];   // the lane's whole parameter column
-#endif
   const long long t0 = so.cyc ? clock64() : 0;
   State16<float> L = load_state16<float>(c, D.base, D.leg);
   rollout_steps16(c, K, L, D.base, D.leg, D.ring, D.ctl, D.ictl, D.legctl, D.etgp, n_steps, obs);   // (stores the state itself: stop_at_done)
@@ -1473,6 +1455,10 @@ struct RecOut { float *obs, *act, *rew; uint8_t* done; const float* noise; const
 // symbols instantiate it: REC is a compile-time constant in each, so the plain kernel contains none of the recording code (a
 // runtime flag in ONE kernel shifts its 512-register allocation; round 2 kept a 70-line copy for that reason, which let fixes
 // diverge).  ps_mem: the [NWP][TM][16] partial sums of the log-std head (REC only).
+// BF16: both kernels pass true -- precision 0 runs the per-wave kernels, so the fp32 tile has no caller and is not instantiated.
+// Its side of the body (the rings started one stage early, policy_core.h: ring_prefetch / head_prefetch) stays as text:
+// without it the compiler orders the instructions of all 12 bf16 tile kernels differently (same registers, same scratch), and
+// these kernels sit at the 512-register limit -- profiles/dead_paths_isa_identity.txt has the comparison.
 template <bool FLAT, bool BF16, bool KNEE, bool PLAIN, bool REC>
 __device__ __forceinline__ void rollout_policy16_body(const KCfg& K, const DevState& D, const PolicyW& P, int n_steps, float act_scale,
                                                       float* obs, const RecOut& R, float* bufA, float* bufB, float (*part)[pol::TM][16],
@@ -1599,7 +1585,7 @@ __device__ __forceinline__ void rollout_policy16_body(const KCfg& K, const DevSt
 #endif
 }
 
-template <bool FLAT, bool BF16, bool KNEE, bool PLAIN>
+template <bool FLAT, bool KNEE, bool PLAIN>
 __global__ void __launch_bounds__(256) k_rollout_policy16(KCfg K, DevState D, PolicyW P, int n_steps, float act_scale, float* obs) {
   using namespace pol;
   __shared__ __attribute__((aligned(16))) float bufA[TM * HS];
@@ -1609,7 +1595,7 @@ __global__ void __launch_bounds__(256) k_rollout_policy16(KCfg K, DevState D, Po
   __shared__ float obs_lds[TM * ETG_OBS_DIM];
   __shared__ float lds_par[4 * LDS16_FIELDS * 64];
   __shared__ float live_lds[TM];
-  rollout_policy16_body<FLAT, BF16, KNEE, PLAIN, false>(K, D, P, n_steps, act_scale, obs, RecOut{}, bufA, bufB, part, nullptr, act_lds, obs_lds, lds_par, live_lds);
+  rollout_policy16_body<FLAT, true, KNEE, PLAIN, false>(K, D, P, n_steps, act_scale, obs, RecOut{}, bufA, bufB, part, nullptr, act_lds, obs_lds, lds_par, live_lds);
 }
 
 // ---- closed loop, precision 0, the 16-lane mapping: ONE WAVE per workgroup, the policy tile per wave (policy_core.h: wave_layer).
@@ -2001,7 +1987,7 @@ __global__ void __launch_bounds__(256) k_rollout_policy4(KCfg K, DevState D, Pol
 }
 
 // the recording variant of k_rollout_policy16 (etg_rollout_policy_record): the same body with REC = true
-template <bool FLAT, bool BF16, bool KNEE, bool PLAIN>
+template <bool FLAT, bool KNEE, bool PLAIN>
 __global__ void __launch_bounds__(256) k_rollout_policy16_rec(KCfg K, DevState D, PolicyW P, int n_steps, float act_scale, float* obs, RecOut R) {
   using namespace pol;
   __shared__ __attribute__((aligned(16))) float bufA[TM * HS];
@@ -2012,7 +1998,7 @@ __global__ void __launch_bounds__(256) k_rollout_policy16_rec(KCfg K, DevState D
   __shared__ float obs_lds[TM * ETG_OBS_DIM];
   __shared__ float lds_par[4 * LDS16_FIELDS * 64];
   __shared__ float live_lds[TM];
-  rollout_policy16_body<FLAT, BF16, KNEE, PLAIN, true>(K, D, P, n_steps, act_scale, obs, R, bufA, bufB, part, part_s, act_lds, obs_lds, lds_par, live_lds);
+  rollout_policy16_body<FLAT, true, KNEE, PLAIN, true>(K, D, P, n_steps, act_scale, obs, R, bufA, bufB, part, part_s, act_lds, obs_lds, lds_par, live_lds);
 }
 
 // Gaussian sensor noise on freshly written observation rows: one thread per (robot, channel).  A separate tiny
@@ -2291,14 +2277,6 @@ __global__ void __launch_bounds__(256) k_term_ctx(KCfg K, DevState D, const uint
   ETG_TPL_##S3 __global__ void KERN<false, true, true>(__VA_ARGS__);           \
   ETG_TPL_##S4 __global__ void KERN<false, false, true>(__VA_ARGS__);          \
   ETG_TPL_##S5 __global__ void KERN<false, true, false>(__VA_ARGS__);
-// closed-loop 16-lane families: <FLAT, BF16, KNEE, PLAIN>, one precision per row
-#define ETG_INSTP16(KERN, BF, S0, S1, S2, S3, S4, S5, ...)                     \
-  ETG_TPL_##S0 __global__ void KERN<true, BF, true, true>(__VA_ARGS__);        \
-  ETG_TPL_##S1 __global__ void KERN<true, BF, false, true>(__VA_ARGS__);       \
-  ETG_TPL_##S2 __global__ void KERN<true, BF, true, false>(__VA_ARGS__);       \
-  ETG_TPL_##S3 __global__ void KERN<false, BF, true, true>(__VA_ARGS__);       \
-  ETG_TPL_##S4 __global__ void KERN<false, BF, false, true>(__VA_ARGS__);      \
-  ETG_TPL_##S5 __global__ void KERN<false, BF, true, false>(__VA_ARGS__);
 // 4-lane families: <FLAT, PLAIN, BODY> in the order of ETG_VARIANTS4 (etg_layout.h)
 #define ETG_INST4(KERN, S0, S1, S2, S3, S4, S5, S6, S7, ...)                   \
   ETG_TPL_##S0 __global__ void KERN<true, false, 3>(__VA_ARGS__);              \
@@ -2328,10 +2306,8 @@ ETG_INST16(k_rollout_policy16w_rec, 7, 2, 4, 6, 1, 3, ETG_ARGS_POLICY_REC)
 ETG_INST16(k_step_policy16, 3, 5, 7, 2, 4, 6, ETG_ARGS_STEP_POLICY)
 ETG_INST16(k_step_policy16_ar, 6, 1, 3, 5, 7, 2, ETG_ARGS_STEP_POLICY_AR)
 ETG_INST16(k_collect_policy16, 4, 6, 1, 3, 5, 7, ETG_ARGS_COLLECT)
-ETG_INSTP16(k_rollout_policy16, false, 2, 3, 4, 5, 6, 7, ETG_ARGS_POLICY)
-ETG_INSTP16(k_rollout_policy16, true, 1, 2, 3, 4, 5, 6, ETG_ARGS_POLICY)
-ETG_INSTP16(k_rollout_policy16_rec, false, 7, 1, 2, 3, 4, 5, ETG_ARGS_POLICY_REC)
-ETG_INSTP16(k_rollout_policy16_rec, true, 6, 7, 1, 2, 3, 4, ETG_ARGS_POLICY_REC)
+ETG_INST16(k_rollout_policy16, 1, 2, 3, 4, 5, 6, ETG_ARGS_POLICY)
+ETG_INST16(k_rollout_policy16_rec, 6, 7, 1, 2, 3, 4, ETG_ARGS_POLICY_REC)
 ETG_INST4(k_settle, 5, 6, 7, 1, 2, 3, 4, 5, ETG_ARGS_SETTLE)
 ETG_INST4(k_finish, 6, 7, 1, 2, 3, 4, 5, 6, ETG_ARGS_FINISH)
 ETG_INST4(k_step, 7, 1, 2, 3, 4, 5, 6, 7, ETG_ARGS_STEP)
@@ -3036,7 +3012,7 @@ static PolicyW policy_wave(const EtgPolicy* pol, int obs_col0) {
 static int rollout_policy16(EtgHandle* h, EtgPolicy* pol, int n_steps, float act_scale, int precision, int obs_col0, float* obs,
                             const RecOut* rec, float* ret, int32_t* len, void* stream) {
   const bool bf = precision != 0;
-  const bool per_wave = precision == 0 && pol->in_dim <= 4 * pol::KQ1 && pol->out_dim <= 12;
+  const bool per_wave = precision == 0;   // (policy_checks has refused every policy the per-wave tile does not take)
   const PolicyW P = per_wave ? policy_wave(pol, obs_col0) : policy_tile(pol, bf, obs_col0);
   const dim3 g = per_wave ? dim3(h->N / 4) : dim3(h->N / 16), b = per_wave ? dim3(BLOCK) : dim3(256);
   hipStream_t s = (hipStream_t)stream;
@@ -3046,17 +3022,15 @@ static int rollout_policy16(EtgHandle* h, EtgPolicy* pol, int n_steps, float act
     if (rec)
       R = {rec->obs + (size_t)d0 * N * ETG_OBS_DIM, rec->act + (size_t)d0 * N * ETG_ACT_DIM, rec->rew + (size_t)d0 * N, rec->done + (size_t)d0 * N,
            rec->noise ? rec->noise + (size_t)d0 * N * ETG_ACT_DIM : nullptr,
-           (const float4*)(per_wave ? pol->w3sq : (bf ? pol->w3sh : pol->w3s)), pol->b3s};
+           (const float4*)(per_wave ? pol->w3sq : pol->w3sh), pol->b3s};
     dispatch16(h->K, [&](auto f_, auto k_, auto p_) {
       constexpr bool F = ETG_V(f_), KN = ETG_V(k_), PL = ETG_V(p_);
       if (rec) {
         if (per_wave) hipLaunchKernelGGL((k_rollout_policy16w_rec<F, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs, R);
-        else if (!bf) hipLaunchKernelGGL((k_rollout_policy16_rec<F, false, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs, R);
-        else hipLaunchKernelGGL((k_rollout_policy16_rec<F, true, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs, R);
+        else hipLaunchKernelGGL((k_rollout_policy16_rec<F, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs, R);
       } else {
         if (per_wave) hipLaunchKernelGGL((k_rollout_policy16w<F, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs);
-        else if (!bf) hipLaunchKernelGGL((k_rollout_policy16<F, false, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs);
-        else hipLaunchKernelGGL((k_rollout_policy16<F, true, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs);
+        else hipLaunchKernelGGL((k_rollout_policy16<F, KN, PL>), g, b, 0, s, h->K, h->D, P, m, act_scale, obs);
       }
     });
     launch_rollout_noise(h, m, obs, s);   // every chunk ends in the caller's rows: the next chunk reads them
@@ -3112,6 +3086,20 @@ extern "C" int etg_rollout_policy_record(EtgHandle* h, EtgPolicy* pol, int n_ste
   return rollout_policy16(h, pol, n_steps, act_scale, precision, obs_col0, obs, &rec, ret, len, stream);
 }
 
+// The refusals that etg_step_policy and the collect entry points share, in this order (k_step_policy16 / k_collect_policy16 run
+// the fp32 per-wave actor tile only; policy_checks has already refused a policy wider than its 64 columns)
+static int step_policy_checks(const char* fn_, const EtgHandle* h, const EtgPolicy* pol, int precision, int obs_col0, const float* noise) {
+  const std::string fn(fn_);
+  if (noise && !pol->has_std) return fail(ETG_ERR_STATE, fn + ": sampling needs etg_policy_load_std() first");
+  if (int rc = policy_checks(fn_, h, pol, obs_col0)) return rc;
+  if (precision != 0) return fail(ETG_ERR_BAD_ARG, fn + ": the kernel runs the fp32 per-wave actor tile: precision 0, in_dim <= 64");
+  if (h->lanes != 16 || h->N % 16 != 0)
+    return fail(ETG_ERR_BAD_ARG, fn + ": needs the 16-lanes-per-robot mapping and num_envs % 16 == 0");
+  if (h->K.motor_mode == 2) return fail(ETG_ERR_BAD_ARG, fn + ": the HYBRID motor mode is not covered (its action has 60 columns)");
+  if (h->K.noise_on) return fail(ETG_ERR_BAD_ARG, fn + ": sensor noise is not covered: switch it off or step");
+  return ETG_OK;
+}
+
 // One closed-loop control step of every robot (include/etgsim_step_policy.h): k_step_policy16 / k_step_policy16_ar, one launch
 // (auto_reset without a cached settle for every robot: the step launch, then etg_reset masked by `done`, as etg_step_autoreset)
 extern "C" int etg_step_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int auto_reset,
@@ -3121,14 +3109,7 @@ extern "C" int etg_step_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, in
   if (!pol || !obs || !terminal_obs || !reward || !done)
     return fail(ETG_ERR_BAD_ARG, "etg_step_policy: policy, obs, terminal_obs, reward and done must be non-null");
   if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_step_policy: call etg_reset first");
-  if (noise && !pol->has_std) return fail(ETG_ERR_STATE, "etg_step_policy: sampling needs etg_policy_load_std() first");
-  if (int rc = policy_checks("etg_step_policy", h, pol, obs_col0)) return rc;
-  if (precision != 0 || pol->in_dim > 4 * pol::KQ1)
-    return fail(ETG_ERR_BAD_ARG, "etg_step_policy: the kernel runs the fp32 per-wave actor tile: precision 0, in_dim <= 64");
-  if (h->lanes != 16 || h->N % 16 != 0)
-    return fail(ETG_ERR_BAD_ARG, "etg_step_policy: needs the 16-lanes-per-robot mapping and num_envs % 16 == 0");
-  if (h->K.motor_mode == 2) return fail(ETG_ERR_BAD_ARG, "etg_step_policy: the HYBRID motor mode is not covered (its action has 60 columns)");
-  if (h->K.noise_on) return fail(ETG_ERR_BAD_ARG, "etg_step_policy: sensor noise is not covered: switch it off or step");
+  if (int rc = step_policy_checks("etg_step_policy", h, pol, precision, obs_col0, noise)) return rc;
   if (auto_reset) refresh_all_cached(h);
   const bool fused_reset = auto_reset && h->all_cached;
   advance_obs_stream(h, fused_reset ? 2 : 1);
@@ -3163,14 +3144,7 @@ static int collect_policy_launch(const char* fn_, EtgHandle* h, EtgPolicy* pol, 
     return fail(ETG_ERR_BAD_ARG, fn + ": policy, obs and the eight record arrays must be non-null");
   if (n_steps < 1) return fail(ETG_ERR_BAD_ARG, fn + ": n_steps must be at least 1");
   if (!h->was_reset) return fail(ETG_ERR_STATE, fn + ": call etg_reset first");
-  if (noise && !pol->has_std) return fail(ETG_ERR_STATE, fn + ": sampling needs etg_policy_load_std() first");
-  if (int rc = policy_checks(fn_, h, pol, obs_col0)) return rc;
-  if (precision != 0 || pol->in_dim > 4 * pol::KQ1)
-    return fail(ETG_ERR_BAD_ARG, fn + ": the kernel runs the fp32 per-wave actor tile: precision 0, in_dim <= 64");
-  if (h->lanes != 16 || h->N % 16 != 0)
-    return fail(ETG_ERR_BAD_ARG, fn + ": needs the 16-lanes-per-robot mapping and num_envs % 16 == 0");
-  if (h->K.motor_mode == 2) return fail(ETG_ERR_BAD_ARG, fn + ": the HYBRID motor mode is not covered (its action has 60 columns)");
-  if (h->K.noise_on) return fail(ETG_ERR_BAD_ARG, fn + ": sensor noise is not covered: switch it off or step");
+  if (int rc = step_policy_checks(fn_, h, pol, precision, obs_col0, noise)) return rc;
   if (h->NX.ok)
     return fail(ETG_ERR_STATE, fn + ": the handle has prepared next-episode dynamics (etg_prepare_next_dynamics): a second "
                                "restart inside the launch would find no prepared row -- use etg_step_policy");

@@ -877,7 +877,8 @@ def test_fused_policy_rollout_equals_predict_and_step():
 
 
 def test_fused_rollouts_on_terrain_match_stepping():
-    """the heightfield instantiations of the fused kernels (k_rollout16<false>, k_rollout_policy16<false, *>)"""
+    """the heightfield instantiations of the fused kernels (k_rollout16<false, *>, k_rollout_policy16w<false, *> and, with bf16
+    operands, the 16-robot tile k_rollout_policy16<false, *>)"""
     _need_gpu()
     from paddlerobotics_amd.policy import MfmaPolicy
     n = 32

@@ -63,7 +63,7 @@ def _oracle_closed_loop(orc, ws, steps):
 
 @pytest.mark.parametrize("n", [64, 4096])
 def test_closed_loop_fused_kernel_and_stepping_match_oracle(n):
-    """configs[2]: etg_rollout_policy (k_rollout_policy16) and predict()+step() against the oracle's closed loop.
+    """configs[2]: etg_rollout_policy (k_rollout_policy16w) and predict()+step() against the oracle's closed loop.
     Bounds after 12 control steps (156 ticks): joint angles 5e-5 rad (median 1e-5), base position 1e-5 m -- 20-100x
     inside the 1e-3 of SURVEY 8d and ~10x the measured error; returns 1e-3 relative + 5e-3."""
     _need_gpu()

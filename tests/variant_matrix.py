@@ -3,7 +3,7 @@
 etg_kernels.hip instantiates every tick-kernel template once per compile-time variant (ETG_VARIANTS16 / ETG_VARIANTS4 of
 etg_layout.h), and every instantiation is a code object of its own: its own register allocation, spills and `if constexpr`
 paths.  This module names, for every variant, a configuration that dispatches to it (CONFIGS), for every C-ABI call that
-launches a tick kernel the template it launches (ENTRY_POINTS), and the instantiations no call can launch (UNREACHED).  A cell
+launches a tick kernel the template it launches (ENTRY_POINTS).  A cell
 of the matrix is (config, entry point): ONE control step from a synchronised state, judged by tests/parity_util.one_step_verdict
 against an OracleEnsemble built from the configuration's own EtgConfig -- the recipe of tests/test_gpu_parity5.py:
 
@@ -322,8 +322,8 @@ def _plain(k16, k4):
 
 
 def _with_bf(k16, k4, bf):
-    # <FLAT, BF16, KNEE, PLAIN> / <FLAT, BF16, PLAIN, BODY>
-    return lambda lanes, v: [(k16 if lanes == 16 else k4, (v[0], bf) + tuple(v[1:]))]
+    # the 4-lane closed-loop kernel has both precisions: <FLAT, BF16, PLAIN, BODY>; the 16-lane tile is bf16 only: <FLAT, KNEE, PLAIN>
+    return lambda lanes, v: [(k16, v) if lanes == 16 else (k4, (v[0], bf) + tuple(v[1:]))]
 
 
 class EntryPoint:
@@ -410,14 +410,14 @@ ENTRY_POINTS = [
     EntryPoint("step_autoreset", BOTH, _plain("k_step16_ar", "k_step_ar"), _run_step, auto_reset=True),
     EntryPoint("rollout_openloop", BOTH, _plain("k_rollout16", "k_rollout"), _run_openloop),
     EntryPoint("rollout_actions", BOTH, _plain("k_rollout_actions16", "k_rollout_actions"), _run_actions),
-    # precision 0 on 16 lanes is the per-wave kernel (rollout_policy16: per_wave), on 4 lanes the fp32 tile
-    EntryPoint("rollout_policy-p0", BOTH, lambda lanes, v: [("k_rollout_policy16w", v)] if lanes == 16 else
-               [("k_rollout_policy4", (v[0], 0) + tuple(v[1:]))], _run_policy(0), body3=False, actor="const"),
+    # precision 0 on 16 lanes is the per-wave kernel (rollout_policy16: per_wave), on 4 lanes the fp32 tile; precision 1 on 16
+    # lanes is the bf16 16-robot tile, the only k_rollout_policy16 / k_rollout_policy16_rec there is
+    EntryPoint("rollout_policy-p0", BOTH, _with_bf("k_rollout_policy16w", "k_rollout_policy4", 0), _run_policy(0), body3=False, actor="const"),
     EntryPoint("rollout_policy-p1", BOTH, _with_bf("k_rollout_policy16", "k_rollout_policy4", 1), _run_policy(1), body3=False, actor="const"),
     EntryPoint("rollout_policy_record-p0", L16, _plain("k_rollout_policy16w_rec", None), _run_record(0, False), actor="mlp"),
     EntryPoint("rollout_policy_record-p0-noise", L16, _plain("k_rollout_policy16w_rec", None), _run_record(0, True), actor="mlp"),
-    EntryPoint("rollout_policy_record-p1", L16, _with_bf("k_rollout_policy16_rec", None, 1), _run_record(1, False), actor="mlp"),
-    EntryPoint("rollout_policy_record-p1-noise", L16, _with_bf("k_rollout_policy16_rec", None, 1), _run_record(1, True), actor="mlp"),
+    EntryPoint("rollout_policy_record-p1", L16, _plain("k_rollout_policy16_rec", None), _run_record(1, False), actor="mlp"),
+    EntryPoint("rollout_policy_record-p1-noise", L16, _plain("k_rollout_policy16_rec", None), _run_record(1, True), actor="mlp"),
     EntryPoint("step_policy-predict", L16, _plain("k_step_policy16", None), _run_step_policy("predict"), actor="mlp"),
     EntryPoint("step_policy-sample", L16, _plain("k_step_policy16", None), _run_step_policy("sample"), actor="mlp"),
     EntryPoint("step_policy_autoreset-predict", L16, _plain("k_step_policy16_ar", None), _run_step_policy("predict"), auto_reset=True, actor="mlp"),
@@ -433,17 +433,6 @@ REFUSALS = [(c, e) for c in CONFIGS for e in ENTRY_POINTS if not e.serves(c)]
 
 def cell_id(config, ep):
     return "%s-%s" % (config.name, ep.name)
-
-
-# Instantiations no C-ABI call can launch.  rollout_policy16 (etg_kernels.hip) takes the per-wave kernels when
-# `precision == 0 && pol->in_dim <= 4 * pol::KQ1 && pol->out_dim <= 12`, and policy_checks -- called by etg_rollout_policy and
-# etg_rollout_policy_record before it -- has already refused in_dim > 4 * KQ1 (= 64) and out_dim != ETG_ACT_DIM (= 12): at
-# precision 0 per_wave is always true, the `else if (!bf)` launches of the fp32 16-robot tile are dead, and the bf16 tile is the
-# only k_rollout_policy16 / k_rollout_policy16_rec anybody runs.
-_FP32_TILE = ("precision 0 always takes the per-wave kernel: per_wave = precision == 0 && in_dim <= 64 && out_dim <= 12 "
-              "(rollout_policy16), and policy_checks refuses in_dim > 64 and out_dim != 12 before it")
-UNREACHED = {(k, (v[0], 0) + tuple(v[1:])): _FP32_TILE
-             for k in ("k_rollout_policy16", "k_rollout_policy16_rec") for v in [c.variant for c in CONFIGS if c.lanes == 16]}
 
 
 def const_policy_action():

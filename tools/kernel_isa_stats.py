@@ -173,7 +173,7 @@ BASELINE_KERNELS = (
     "_ZN3etg8k_step16ILb1ELb0ELb1EEEvNS_4KCfgENS_8DevStateEPKfPKhPfS7_PhS7_",      # k_step16<flat, toe spheres only, plain>
     "_ZN3etg9k_rolloutILb1ELb0ELi1EEEvNS_4KCfgENS_8DevStateEiPfNS_7StatOutE",      # k_rollout<flat, all options, body rows>: the 4-lane mapping (> 4096 robots)
     "_ZN3etg19k_rollout_policy16wILb1ELb1ELb1EEEvNS_4KCfgENS_8DevStateENS_7PolicyWEifPf",   # closed loop (configs[2]) since round 6: one wave = 4 robots + their policy tile, fp32, body rows; no scratch
-    "_ZN3etg18k_rollout_policy16ILb1ELb0ELb1ELb1EEEvNS_4KCfgENS_8DevStateENS_7PolicyWEifPf",   # the workgroup-tile closed loop of rounds 3-5 (kept for bf16 operands), body rows
+    "_ZN3etg18k_rollout_policy16ILb1ELb1ELb1EEEvNS_4KCfgENS_8DevStateENS_7PolicyWEifPf",   # the workgroup-tile closed loop of rounds 3-5 (kept for bf16 operands: the only precision it has), body rows
 )
 
 
