@@ -90,9 +90,11 @@ extern "C" int etg_fit_etg(const double* points, int nb, const double* feats, co
     return ETG_ERR_BAD_ARG;
   }
   // launch on the device that owns the buffers (the caller's current device may be another one): the other entry
-  // points bind their handle's device the same way
+  // points bind their handle's device the same way.  The query alone is no proof: it can succeed for a host pointer that was
+  // never registered (type hipMemoryTypeUnregistered), so the type is required to be device memory
   hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, points) != hipSuccess || hipSetDevice(attr.device) != hipSuccess) {
+  if (hipPointerGetAttributes(&attr, points) != hipSuccess || attr.type != hipMemoryTypeDevice ||
+      hipSetDevice(attr.device) != hipSuccess) {
     (void)hipGetLastError();
     etg_set_last_error_("etg_fit_etg: points is not a device pointer");
     return ETG_ERR_BAD_ARG;

@@ -222,10 +222,12 @@ int fail(const char* msg) {
   etg_set_last_error_(msg);
   return ETG_ERR_BAD_ARG;
 }
-// launch on the device that owns the memory (the caller's current device may be another one)
+// launch on the device that owns the memory (the caller's current device may be another one).  The query can succeed for a
+// host pointer that was never registered (type hipMemoryTypeUnregistered): only device memory is accepted
 bool bind_device(const void* p) {
   hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) == hipSuccess && hipSetDevice(attr.device) == hipSuccess) return true;
+  if (hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice &&
+      hipSetDevice(attr.device) == hipSuccess) return true;
   (void)hipGetLastError();
   return false;
 }

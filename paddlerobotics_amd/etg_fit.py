@@ -45,7 +45,8 @@ def opt_with_points_batched(ETG, ETG_T, points, b0, w0, precision=1e-4, lamb=0.5
     if key not in cache:
         cache[key] = torch.as_tensor(np.array([ETG.update(t) for t in control_times(ETG_T)]), dtype=torch.float64, device=device)
     else:
-        ETG.t += ETG.dt * len(control_times(ETG_T))       # (what the update() calls of the uncached path do to the layer's clock)
+        for _ in control_times(ETG_T):                    # what the update() calls of the uncached path do to the layer's clock:
+            ETG.t += ETG.dt                               # one addition per call (t + 6 dt rounds differently)
     feats = cache[key]
     pts = torch.as_tensor(points, dtype=torch.float64, device=device)
     if pts.is_cuda:
