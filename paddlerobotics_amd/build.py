@@ -9,7 +9,7 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 SOURCES = ["etg_kernels.hip", "policy_mlp.hip", "etg_fit.hip", "etg_replay.hip", "etg_render.hip", "sac_learn.hip", "bc_learn.hip", "etg_snapshot.hip", "etg_monitor.hip", "etg_nstep.hip", "etg_heightscan.hip", "ppo_learn.hip"]
-HEADERS = ["etg_core.h", "etg_core16.h", "gram16.h", "etg_layout.h", "policy_core.h", "render_core.h", "sac_core.h", "bc_core.h", "ac_learner.h", "snapshot_core.h", "scan_core.h", "ppo_core.h", os.path.join("..", "..", "include", "etgsim.h"),
+HEADERS = ["etg_core.h", "etg_core16.h", "gram16.h", "etg_layout.h", "policy_core.h", "render_core.h", "sac_core.h", "bc_core.h", "ac_learner.h", "dev_buffers.h", "snapshot_core.h", "scan_core.h", "ppo_core.h", os.path.join("..", "..", "include", "etgsim.h"),
            os.path.join("..", "..", "include", "etgsim_step_policy.h"), os.path.join("..", "..", "include", "etgsim_terminal.h"),
            os.path.join("..", "..", "include", "etgsim_render.h"), os.path.join("..", "..", "include", "etgsim_sac.h"),
            os.path.join("..", "..", "include", "etgsim_bc.h"), os.path.join("..", "..", "include", "etgsim_snapshot.h"),

@@ -27,10 +27,9 @@
 #include <vector>
 
 #include "../../include/etgsim_sac.h"
+#include "dev_buffers.h"
 #include "policy_core.h"
 #include "sac_core.h"
-
-extern "C" void etg_set_last_error_(const char* msg);
 
 namespace ac {
 using namespace sac;
@@ -52,20 +51,11 @@ struct Learner {
   size_t off[TENSORS + 1], len[TENSORS];
 };
 
-struct Buf { void** p; size_t bytes; };   // one device buffer of a handle: where its pointer is kept, its size
+using dev::Buf;
 
 namespace {   // each learner's translation unit gets its own copy, as it does of sac_core.h's static kernels
 
-int fail(int code, const char* msg) {
-  etg_set_last_error_(msg);
-  return code;
-}
-
-int fail(int code, const char* who, const char* what) {
-  static thread_local char msg[200];
-  snprintf(msg, sizeof msg, "%s: %s", who, what);
-  return fail(code, msg);
-}
+using dev::alloc; using dev::fail; using dev::release;   // dev_buffers.h: a handle's buffers, allocated + zeroed / freed from one list
 
 // offsets and lengths of the 20 tensors of a model of observation width d; off[TENSORS] = the arena's size
 void layout(size_t d, size_t* off, size_t* len) {
@@ -78,19 +68,6 @@ void layout(size_t d, size_t* off, size_t* len) {
 }
 
 // ------------------------------------------------------------------------------------------------- creating and destroying
-int alloc(const std::vector<Buf>& bufs, const char* who) {
-  for (const Buf& x : bufs) {
-    if (hipMalloc(x.p, x.bytes) != hipSuccess) return fail(ETG_ERR_ALLOC, who, "hipMalloc failed");
-    if (hipMemset(*x.p, 0, x.bytes) != hipSuccess) return fail(ETG_ERR_HIP, who, "hipMemset failed");
-  }
-  return ETG_OK;
-}
-
-void release(const std::vector<Buf>& bufs) {
-  for (const Buf& x : bufs)
-    if (*x.p) (void)hipFree(*x.p);
-}
-
 std::vector<Buf> buffers(Learner* h) {
   const size_t B = h->maxb, n = h->total * 4;
   return {{(void**)&h->P, n}, {(void**)&h->G, n}, {(void**)&h->M, n}, {(void**)&h->V, n},

@@ -2327,46 +2327,82 @@ ETG_INSTP4(k_rollout_policy4, true, 3, 4, 5, 6, 7, 1, ETG_ARGS_POLICY)
 #include "../../include/etgsim_snapshot.h"
 #include "scan_core.h"
 #include "../../include/etgsim_heightscan.h"
+#include "dev_buffers.h"
 #include <string.h>
 
 // ====================================================================== C ABI
 using namespace etg;
 
-struct EtgHandle {
-  int device;
-  int N;
+struct EtgHandle {   // etg_create's `new EtgHandle()` zeroes the members without an initialiser (K, M, D, NX: every pointer null)
+  int device = 0, N = 0;
   KCfg K;
   ModelF M;
   DevState D;
-  float* hf;
-  int lanes;                    // 4 or 16 lanes per robot (EtgConfig.lanes_per_robot)
-  unsigned long long push_calls;  // stream position of etg_random_pushes
-  unsigned obs_calls;             // stream position of the sensor noise: observations written so far
-  bool was_reset;                 // etg_step before the first etg_reset is a caller error (state undefined)
-  bool fext_set, push_on;         // a set force / random pushes are installed: K.ext_force = fext_set || push_on
-  bool all_cached;                // every robot has a valid cached settle (true after a full etg_reset until parameters,
-                                  // terrain or -- on a heightfield -- start offsets change): etg_step_autoreset's fast path
+  float* hf = nullptr;
+  int lanes = 0;                      // 4 or 16 lanes per robot (EtgConfig.lanes_per_robot)
+  unsigned long long push_calls = 0;  // stream position of etg_random_pushes
+  unsigned obs_calls = 0;             // stream position of the sensor noise: observations written so far
+  bool was_reset = false;             // etg_step before the first etg_reset is a caller error (state undefined)
+  bool fext_set = false, push_on = false;   // a set force / random pushes are installed: K.ext_force = fext_set || push_on
+  bool all_cached = false;            // every robot has a valid cached settle (true after a full etg_reset until parameters,
+                                      // terrain or -- on a heightfield -- start offsets change): etg_step_autoreset's fast path
   // etg_rollout_wave_cycles: [launches of the last open-loop rollout][wavefronts] shader-clock cycles, written by the launches
-  long long* wave_cycles;
-  int wc_cap, wc_launches, wc_waves;
-  int rollout_chunk;            // control steps per fused launch (400: one launch for BASELINE's episode; 25 .. 400 measured, profiles/r06_chunk_sweep.txt; ETG_ROLLOUT_CHUNK overrides it: a measurement aid)
-  float *tmp_obs, *tmp_reward;  // sinks for etg_rollout_openloop
-  uint8_t* tmp_done;
+  long long* wave_cycles = nullptr;
+  int wc_cap = 0, wc_launches = 0, wc_waves = 0;
+  int rollout_chunk = 400;      // control steps per fused launch (400: one launch for BASELINE's episode, ~37 ms: fewer launches = fewer chip-wide barriers, 93.3 us per step against 94.0 at 50; 25 .. 400 measured, profiles/r06_chunk_sweep.txt; ETG_ROLLOUT_CHUNK overrides it: a measurement aid)
+  float *tmp_obs = nullptr, *tmp_reward = nullptr;  // sinks for etg_rollout_openloop
+  uint8_t* tmp_done = nullptr;
   // etg_prepare_next_dynamics: rows waiting for the robots' next episodes + the scratch state / ring / flags its settle runs on
   NextDyn NX;
-  float *nx_base, *nx_leg, *nx_ring;
-  unsigned char* nx_cache_ok;
-  uint8_t* nx_mask;       // etg_prepare_next_dynamics: the call's mask without the robots whose episode is younger than the ring
+  float *nx_base = nullptr, *nx_leg = nullptr, *nx_ring = nullptr;
+  unsigned char* nx_cache_ok = nullptr;
+  uint8_t* nx_mask = nullptr;   // etg_prepare_next_dynamics: the call's mask without the robots whose episode is younger than the ring
   // all_cached again after MASKED resets: every invalidation bumps inval_seq; a masked etg_reset ends with a count of the robots
   // still without a cached settle, written with the sequence number it ran under to pinned host memory (cached_report[0] = count,
   // [1] = seq); the next etg_step_autoreset / etg_prepare_next_dynamics trusts a zero count only under the CURRENT number
-  unsigned inval_seq;
-  volatile unsigned* cached_report;   // pinned host memory, also mapped on the device (cached_report_dev)
-  unsigned* cached_report_dev;
+  unsigned inval_seq = 1;
+  volatile unsigned* cached_report = nullptr;   // pinned host memory, also mapped on the device (cached_report_dev)
+  unsigned* cached_report_dev = nullptr;
   // etg_render: lowest / highest height of the heightfield, taken at the first render after etg_set_heightfield
-  bool hf_range_ok;
-  float hf_lo, hf_hi;
+  bool hf_range_ok = false;
+  float hf_lo = 0.0f, hf_hi = 0.0f;
 };
+
+// ---- the handle's per-robot device arrays, ONE row each, for everything that has to know them all: etg_create allocates the
+// CORE group, ensure_next_arrays the NEXT group (on first use), etg_destroy frees every row, snapshot_table takes the RECORD rows,
+// in this order, as the segments of a snapshot record -- so the order of those rows is part of the record format.  The shape is
+// snapshot_core.h's and gives the size too: rows * per * N words, or N bytes.  SCRATCH, in no record: tmp_* (sinks of
+// etg_rollout_openloop), nx_base .. nx_mask (the prepared settle's state, dead when etg_prepare_next_dynamics returns).  Not in
+// the table, freed by etg_destroy: hf (sized by the heightfield), wave_cycles (per rollout call), cached_report (pinned host memory).
+enum ArrayGroup { CORE = 1, NEXT = 2 };
+enum ArrayUse { SCRATCH, RECORD };
+struct HandleArray {
+  size_t slot;   // where the handle keeps the pointer: its offset in EtgHandle
+  int rows, per;
+  bool bytes;    // the slot points at one-byte elements, a flag array (rows = per = 1)
+  ArrayGroup group; ArrayUse use;
+};
+#define ARR(m, rows, per, group, use) HandleArray{offsetof(EtgHandle, m), rows, per, sizeof(*((EtgHandle*)nullptr)->m) == 1, group, use}
+static constexpr HandleArray kHandleArrays[] = {
+    ARR(D.base, BS_N, 1, CORE, RECORD),       ARR(D.leg, LG_N, 4, CORE, RECORD),       ARR(D.ctl, CT_N, 1, CORE, RECORD),
+    ARR(D.ictl, IC_N, 1, CORE, RECORD),       ARR(D.legctl, LC_N, 4, CORE, RECORD),    ARR(D.etgp, EP_N, 1, CORE, RECORD),
+    ARR(D.par, PR_N, 4, CORE, RECORD),        ARR(D.ring, RING * 8, 4, CORE, RECORD),  ARR(D.dyn, 1, ETG_DYN_DIM, CORE, RECORD),
+    ARR(D.cache_base, BS_N, 1, CORE, RECORD), ARR(D.cache_leg, LG_N, 4, CORE, RECORD), ARR(D.cache_ring, RING * 8, 4, CORE, RECORD),
+    ARR(D.cache_ok, 1, 1, CORE, RECORD),      ARR(D.reset_off, 2, 1, CORE, RECORD),    ARR(D.cache_off, FIN_ROWS, 1, CORE, RECORD),
+    ARR(tmp_obs, 1, ETG_OBS_DIM, CORE, SCRATCH), ARR(tmp_reward, 1, 1, CORE, SCRATCH), ARR(tmp_done, 1, 1, CORE, SCRATCH),
+    ARR(NX.par, PR_N, 4, NEXT, RECORD),       ARR(NX.dyn, 1, ETG_DYN_DIM, NEXT, RECORD), ARR(NX.ok, 1, 1, NEXT, RECORD),
+    ARR(nx_base, BS_N, 1, NEXT, SCRATCH),     ARR(nx_leg, LG_N, 4, NEXT, SCRATCH),     ARR(nx_ring, RING * 8, 4, NEXT, SCRATCH),
+    ARR(nx_cache_ok, 1, 1, NEXT, SCRATCH),    ARR(nx_mask, 1, 1, NEXT, SCRATCH)};   // (nx_mask last: ensure_next_arrays)
+#undef ARR
+static_assert([] { int n = 0; for (const HandleArray& a : kHandleArrays) n += a.use == RECORD; return n; }() <= snapshot::kMaxSegs,
+              "snapshot::Table is too small for the RECORD rows");
+static void** array_slot(EtgHandle* h, const HandleArray& a) { return (void**)((char*)h + a.slot); }
+static std::vector<dev::Buf> array_bufs(EtgHandle* h, int groups) {   // the rows of the given groups as buffers, sized by their shapes
+  std::vector<dev::Buf> bufs;
+  for (const HandleArray& a : kHandleArrays)
+    if (a.group & groups) bufs.push_back({array_slot(h, a), a.bytes ? (size_t)h->N : (size_t)a.rows * a.per * h->N * 4});
+  return bufs;
+}
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
@@ -2430,24 +2466,6 @@ extern "C" int etg_create(const EtgConfig* cfg, const EtgRobotModel* model, int 
   h->N = cfg->num_envs;
   h->K = make_kcfg(*cfg, *model);
   h->M = make_modelf(*model);
-  h->hf = nullptr;
-  h->push_calls = 0;
-  h->obs_calls = 0;
-  h->was_reset = false;
-  h->fext_set = h->push_on = false;
-  h->all_cached = false;
-  h->NX = NextDyn{nullptr, nullptr, nullptr};
-  h->inval_seq = 1;
-  h->cached_report = nullptr;
-  h->cached_report_dev = nullptr;
-  h->nx_base = h->nx_leg = h->nx_ring = nullptr;
-  h->nx_cache_ok = nullptr;
-  h->nx_mask = nullptr;
-  h->wave_cycles = nullptr;
-  h->wc_cap = h->wc_launches = h->wc_waves = 0;
-  h->hf_range_ok = false;
-  h->hf_lo = h->hf_hi = 0.0f;
-  h->rollout_chunk = 400;  // (a 400-step launch lasts ~37 ms; fewer launches = fewer chip-wide barriers: 93.3 us per step against 94.0 at 50)
   if (const char* e = getenv("ETG_ROLLOUT_CHUNK")) {
     const int v = atoi(e);
     if (v >= 1 && v <= 100000) h->rollout_chunk = v;
@@ -2461,34 +2479,27 @@ extern "C" int etg_create(const EtgConfig* cfg, const EtgRobotModel* model, int 
   const int auto16 = (cfg->body_contacts == 1 || cfg->body_contacts == 2) ? 8192 : 4096;
   h->lanes = cfg->lanes_per_robot != 0 ? cfg->lanes_per_robot : (cfg->num_envs <= auto16 ? 16 : 4);
   if (cfg->body_contacts == 3) h->lanes = 4;   // six rows per leg: the 16-lane mapping has one spare lane per leg
-  size_t N = h->N, NL = 4 * N;
-  struct { void** p; size_t bytes; } allocs[] = {
-      {(void**)&h->D.base, BS_N * N * 4},   {(void**)&h->D.leg, LG_N * NL * 4},   {(void**)&h->D.ctl, CT_N * N * 4},
-      {(void**)&h->D.ictl, IC_N * N * 4},   {(void**)&h->D.legctl, LC_N * NL * 4}, {(void**)&h->D.etgp, EP_N * N * 4},
-      {(void**)&h->D.par, PR_N * NL * 4},   {(void**)&h->D.ring, (size_t)RING * 8 * NL * 4}, {(void**)&h->D.dyn, ETG_DYN_DIM * N * 4},
-      {(void**)&h->D.cache_base, BS_N * N * 4}, {(void**)&h->D.cache_leg, LG_N * NL * 4},
-      {(void**)&h->D.cache_ring, (size_t)RING * 8 * NL * 4}, {(void**)&h->D.cache_ok, N},
-      {(void**)&h->D.reset_off, 2 * N * 4}, {(void**)&h->D.cache_off, (size_t)FIN_ROWS * N * 4},
-      {(void**)&h->tmp_obs, ETG_OBS_DIM * N * 4}, {(void**)&h->tmp_reward, N * 4}, {(void**)&h->tmp_done, N}};
-  for (auto& a : allocs) {
-    if (hipMalloc(a.p, a.bytes) != hipSuccess) return fail(ETG_ERR_ALLOC, "etg_create: hipMalloc failed");
-    HIP_TRY(hipMemset(*a.p, 0, a.bytes));
-  }
-  h->K.cring = h->D.cache_ring;
-  // default physical parameters = param2dynamic_dict(zeros(48)) (train.py:112-126)
-  std::vector<float> row(ETG_DYN_DIM, 1.0f);
-  row[0] = 40.0f; row[1] = 0.2f; row[2] = 1.5f;
-  for (int j = 0; j < 12; j++) { row[21 + j] = 80.0f; row[33 + j] = (j % 3 == 0) ? 1.0f : 2.0f; }
-  row[45] = 0.0f; row[46] = 0.0f; row[47] = -10.0f;
-  std::vector<float> dyn(N * ETG_DYN_DIM);
-  for (size_t i = 0; i < N; i++) std::copy(row.begin(), row.end(), dyn.begin() + i * ETG_DYN_DIM);
-  float* ddyn = nullptr;
-  if (hipMalloc((void**)&ddyn, dyn.size() * 4) != hipSuccess) return fail(ETG_ERR_ALLOC, "etg_create: hipMalloc failed");
-  HIP_TRY(hipMemcpy(ddyn, dyn.data(), dyn.size() * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_set_params, dim3(grid_for(h)), dim3(BLOCK), 0, 0, h->K, h->M, h->D, ddyn, nullptr, nullptr, 0, nullptr);
-  hipLaunchKernelGGL(k_set_strength, dim3((4 * h->N + 255) / 256), dim3(256), 0, 0, h->K, h->D, (const float*)nullptr, (const uint8_t*)nullptr);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipFree(ddyn));
+  float* ddyn = nullptr;   // the default parameter rows on their way to the device
+  int rc = [&]() -> int {  // (HIP_TRY returns from here: whatever fails, the cleanup below runs)
+    if (int r = dev::alloc(array_bufs(h, CORE), "etg_create")) return r;
+    h->K.cring = h->D.cache_ring;
+    // default physical parameters = param2dynamic_dict(zeros(48)) (train.py:112-126)
+    std::vector<float> row(ETG_DYN_DIM, 1.0f);
+    row[0] = 40.0f; row[1] = 0.2f; row[2] = 1.5f;
+    for (int j = 0; j < 12; j++) { row[21 + j] = 80.0f; row[33 + j] = (j % 3 == 0) ? 1.0f : 2.0f; }
+    row[45] = 0.0f; row[46] = 0.0f; row[47] = -10.0f;
+    std::vector<float> dyn((size_t)h->N * ETG_DYN_DIM);
+    for (size_t i = 0; i < dyn.size(); i++) dyn[i] = row[i % ETG_DYN_DIM];
+    if (hipMalloc((void**)&ddyn, dyn.size() * 4) != hipSuccess) return fail(ETG_ERR_ALLOC, "etg_create: hipMalloc failed");
+    HIP_TRY(hipMemcpy(ddyn, dyn.data(), dyn.size() * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_set_params, dim3(grid_for(h)), dim3(BLOCK), 0, 0, h->K, h->M, h->D, ddyn, nullptr, nullptr, 0, nullptr);
+    hipLaunchKernelGGL(k_set_strength, dim3((4 * h->N + 255) / 256), dim3(256), 0, 0, h->K, h->D, (const float*)nullptr, (const uint8_t*)nullptr);
+    HIP_TRY(hipDeviceSynchronize());
+    return ETG_OK;
+  }();
+  const hipError_t e = hipFree(ddyn);   // (null, a no-op, when the steps above did not get that far)
+  if (!rc && e != hipSuccess) rc = fail(ETG_ERR_HIP, std::string("hipFree(ddyn): ") + hipGetErrorString(e));
+  if (rc) { etg_destroy(h); return rc; }
   *out = h;
   return ETG_OK;
 }
@@ -2496,11 +2507,9 @@ extern "C" int etg_create(const EtgConfig* cfg, const EtgRobotModel* model, int 
 extern "C" void etg_destroy(EtgHandle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  void* ptrs[] = {h->D.base, h->D.leg, h->D.ctl, h->D.ictl, h->D.legctl, h->D.etgp, h->D.par, h->D.ring, h->hf, h->D.dyn,
-                  h->D.cache_base, h->D.cache_leg, h->D.cache_ring, h->D.cache_ok, h->D.reset_off, h->D.cache_off,
-                  h->tmp_obs, h->tmp_reward, h->tmp_done, h->wave_cycles, h->NX.par, h->NX.dyn, h->NX.ok, h->nx_base, h->nx_leg, h->nx_ring, h->nx_cache_ok, h->nx_mask};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  dev::release(array_bufs(h, CORE | NEXT));
+  if (h->hf) (void)hipFree(h->hf);
+  if (h->wave_cycles) (void)hipFree(h->wave_cycles);
   if (h->cached_report) (void)hipHostFree((void*)h->cached_report);
   delete h;
 }
@@ -2657,6 +2666,11 @@ static inline void refresh_all_cached(EtgHandle* h) {
   if (seq == h->inval_seq && h->cached_report[0] == 0u) h->all_cached = true;
 }
 
+// the NEXT group, allocated and zeroed on the caller's stream on first use (nx_mask, its last row, is null until all of it is there)
+static int ensure_next_arrays(EtgHandle* h, const char* who, hipStream_t s) {
+  return h->nx_mask ? ETG_OK : dev::alloc(array_bufs(h, NEXT), who, &s);
+}
+
 extern "C" int etg_prepare_next_dynamics(EtgHandle* h, const float* dyn, const uint8_t* mask, void* stream) {
   CHECK_HANDLE(h);
   if (!dyn) return fail(ETG_ERR_BAD_ARG, "etg_prepare_next_dynamics: dyn is null");
@@ -2664,18 +2678,9 @@ extern "C" int etg_prepare_next_dynamics(EtgHandle* h, const float* dyn, const u
   if (!h->was_reset || !h->all_cached)
     return fail(ETG_ERR_STATE, "etg_prepare_next_dynamics: every robot needs a valid cached settle (a full etg_reset, or masked resets "
                                "that covered every robot whose parameters, terrain or start offset changed)");
-  const size_t N = h->N, NL = 4 * N;
-  if (!h->NX.par) {
-    struct { void** p; size_t bytes; } allocs[] = {
-        {(void**)&h->NX.par, PR_N * NL * 4}, {(void**)&h->NX.dyn, ETG_DYN_DIM * N * 4}, {(void**)&h->NX.ok, N},
-        {(void**)&h->nx_base, BS_N * N * 4}, {(void**)&h->nx_leg, LG_N * NL * 4}, {(void**)&h->nx_ring, (size_t)RING * 8 * NL * 4},
-        {(void**)&h->nx_cache_ok, N}, {(void**)&h->nx_mask, N}};
-    for (auto& a : allocs) {
-      if (hipMalloc(a.p, a.bytes) != hipSuccess) return fail(ETG_ERR_ALLOC, "etg_prepare_next_dynamics: hipMalloc failed");
-      HIP_TRY(hipMemsetAsync(*a.p, 0, a.bytes, (hipStream_t)stream));
-    }
-  }
+  const size_t NL = 4 * (size_t)h->N;
   hipStream_t s = (hipStream_t)stream;
+  if (int rc = ensure_next_arrays(h, "etg_prepare_next_dynamics", s)) return rc;
   const dim3 ge((h->N + 255) / 256), gc((4 * h->N + 255) / 256);
   // a view of the robot arrays whose parameters are the NEXT rows, whose live state / ring are scratch (the robots keep running
   // on theirs) and whose settle cache is the real one: k_settle* leaves the settled state of the new rows in the cache
@@ -3323,25 +3328,16 @@ extern "C" int etg_set_state(EtgHandle* h, const float* state, void* stream) {
   return ETG_OK;
 }
 
-// ---- snapshots (include/etgsim_snapshot.h): the handle's persistent per-robot arrays as the segments of a record, in the order
-// of etg_create's allocation table followed by etg_prepare_next_dynamics's; the kernel is etg_snapshot.hip's.  Scratch, not in a
-// record: tmp_obs / tmp_reward / tmp_done (sinks of etg_rollout_openloop), nx_base / nx_leg / nx_ring / nx_cache_ok / nx_mask
-// (the state the prepared settle runs on, dead when etg_prepare_next_dynamics returns), wave_cycles, cached_report.
-static snapshot::Table snapshot_table(const EtgHandle* h) {
+// ---- snapshots (include/etgsim_snapshot.h): the RECORD rows of kHandleArrays, in the table's order, as the segments of a
+// record; the kernel is etg_snapshot.hip's.
+static snapshot::Table snapshot_table(EtgHandle* h) {
   snapshot::Table T;
-  const DevState& D = h->D;
   int off = snapshot::kHeadWords, n = 0;
-  auto add = [&](void* p, int rows, int per, int bytes) {
-    T.seg[n++] = snapshot::Seg{p, off, rows, per, bytes};
-    off += rows * per;
-  };
-  add(D.base, BS_N, 1, 0);          add(D.leg, LG_N, 4, 0);             add(D.ctl, CT_N, 1, 0);
-  add(D.ictl, IC_N, 1, 0);          add(D.legctl, LC_N, 4, 0);          add(D.etgp, EP_N, 1, 0);
-  add(D.par, PR_N, 4, 0);           add(D.ring, RING * 8, 4, 0);        add(D.dyn, 1, ETG_DYN_DIM, 0);
-  add(D.cache_base, BS_N, 1, 0);    add(D.cache_leg, LG_N, 4, 0);       add(D.cache_ring, RING * 8, 4, 0);
-  add(D.cache_ok, 1, 1, 1);         add(D.reset_off, 2, 1, 0);          add(D.cache_off, FIN_ROWS, 1, 0);
-  add(h->NX.par, PR_N, 4, 0);       add(h->NX.dyn, 1, ETG_DYN_DIM, 0);  add(h->NX.ok, 1, 1, 1);
-  static_assert(18 <= snapshot::kMaxSegs, "snapshot::Table is too small");
+  for (const HandleArray& a : kHandleArrays) {
+    if (a.use != RECORD) continue;
+    T.seg[n++] = snapshot::Seg{*array_slot(h, a), off, a.rows, a.per, a.bytes};
+    off += a.rows * a.per;
+  }
   T.nseg = n;
   T.row_words = (off + 3) / 4 * 4;
   T.n_env = h->N;
@@ -3455,16 +3451,8 @@ extern "C" int etg_snapshot_restore(EtgHandle* h, const int32_t* env_ids, int n,
           return fail(ETG_ERR_BAD_ARG, "etg_snapshot_restore: a target env id is on another heightfield band than the robot its record was saved from");
     }
   }
-  if (hdr->next_dyn && !h->NX.par) {   // the records carry rows for the next episodes: the arrays of etg_prepare_next_dynamics
-    const size_t N = h->N, NL = 4 * N;
-    struct { void** p; size_t bytes; } allocs[] = {
-        {(void**)&h->NX.par, PR_N * NL * 4}, {(void**)&h->NX.dyn, ETG_DYN_DIM * N * 4}, {(void**)&h->NX.ok, N},
-        {(void**)&h->nx_base, BS_N * N * 4}, {(void**)&h->nx_leg, LG_N * NL * 4}, {(void**)&h->nx_ring, (size_t)RING * 8 * NL * 4},
-        {(void**)&h->nx_cache_ok, N}, {(void**)&h->nx_mask, N}};
-    for (auto& a : allocs) {
-      if (!*a.p && hipMalloc(a.p, a.bytes) != hipSuccess) return fail(ETG_ERR_ALLOC, "etg_snapshot_restore: hipMalloc failed");
-      HIP_TRY(hipMemsetAsync(*a.p, 0, a.bytes, s));
-    }
+  if (hdr->next_dyn && !h->nx_mask) {   // the records carry rows for the next episodes: the arrays of etg_prepare_next_dynamics
+    if (int rc = ensure_next_arrays(h, "etg_snapshot_restore", s)) return rc;
     T = snapshot_table(h);
   }
   HIP_TRY(etg_snapshot_launch(T, env_ids, n, (uint32_t*)const_cast<void*>(rows), 1, s));

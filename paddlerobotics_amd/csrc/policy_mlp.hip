@@ -19,6 +19,7 @@
 #include <string>
 
 #include "../../include/etgsim.h"
+#include "dev_buffers.h"
 #include "policy_core.h"
 
 namespace {
@@ -304,17 +305,23 @@ __global__ void __launch_bounds__(THREADS) k_policy_wide(const float* __restrict
 
 }  // namespace
 
-extern "C" void etg_set_last_error_(const char* msg);
-
 static size_t packed_floats(int ntiles, int nkb) { return (size_t)ntiles * nkb * 64 * 4; }
 
 // k-blocks of layer 1 in w1 / w1h: the 64 padded columns of k_policy (and of the closed-loop kernels that read w1), or k_policy_wide's
 // Kpad / 16
 static int l1_kblocks(int in_dim) { return in_dim <= 64 ? 4 : 2 * ((in_dim + 31) / 32); }
 
-static int pfail(int code, const char* msg) {
-  etg_set_last_error_(msg);
-  return code;
+static int pfail(int code, const char* msg) { return dev::fail(code, msg); }   // (one etg_last_error() serves the whole ABI)
+
+// every device array of a policy (sizes in floats), for etg_policy_create and etg_policy_destroy: the packed fp32 weights and the
+// biases, the bf16 copies (half the floats), the per-wave tile's packings
+static std::vector<dev::Buf> policy_buffers(EtgPolicy* p) {
+  const size_t w1 = packed_floats(HID / 16, l1_kblocks(p->in_dim)), w2 = packed_floats(HID / 16, HID / 16), w3 = packed_floats(1, HID / 16);
+  const size_t hid = p->hidden, out = p->out_dim, w12q = (size_t)KG * NCHW * 256, w3q = (size_t)KQH * 256;
+  auto buf = [](float*& slot, size_t floats) { return dev::Buf{(void**)&slot, floats * 4}; };
+  return {buf(p->w1, w1),      buf(p->b1, hid),     buf(p->w2, w2),      buf(p->b2, hid),      buf(p->w3, w3),
+          buf(p->b3, out),     buf(p->w3s, w3),     buf(p->b3s, out),    buf(p->w1h, w1 / 2),  buf(p->w2h, w2 / 2),
+          buf(p->w3h, w3 / 2), buf(p->w3sh, w3 / 2), buf(p->w12q, w12q), buf(p->w3q, w3q),     buf(p->w3sq, w3q)};
 }
 
 extern "C" int etg_policy_create(int in_dim, int hidden, int out_dim, int device, EtgPolicy** out) {
@@ -324,19 +331,9 @@ extern "C" int etg_policy_create(int in_dim, int hidden, int out_dim, int device
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return pfail(ETG_ERR_NO_DEVICE, "etg_policy_create: no HIP device");
   if (device < 0 || device >= ndev) return pfail(ETG_ERR_BAD_ARG, "etg_policy_create: bad device");
   if (hipSetDevice(device) != hipSuccess) return pfail(ETG_ERR_HIP, "hipSetDevice");
-  EtgPolicy* p = new EtgPolicy();
+  EtgPolicy* p = new EtgPolicy();   // (value-initialised: has_std = 0, every pointer null)
   p->device = device; p->in_dim = in_dim; p->hidden = hidden; p->out_dim = out_dim;
-  const int nkb1 = l1_kblocks(in_dim);
-  struct { float** q; size_t n; } a[] = {{&p->w1, packed_floats(HID / 16, nkb1)}, {&p->b1, (size_t)hidden},
-                                         {&p->w2, packed_floats(HID / 16, HID / 16)}, {&p->b2, (size_t)hidden},
-                                         {&p->w3, packed_floats(1, HID / 16)}, {&p->b3, (size_t)out_dim},
-                                         {&p->w3s, packed_floats(1, HID / 16)}, {&p->b3s, (size_t)out_dim},
-                                         {&p->w1h, packed_floats(HID / 16, nkb1) / 2}, {&p->w2h, packed_floats(HID / 16, HID / 16) / 2},
-                                         {&p->w3h, packed_floats(1, HID / 16) / 2}, {&p->w3sh, packed_floats(1, HID / 16) / 2},
-                                         {&p->w12q, (size_t)KG * NCHW * 256}, {&p->w3q, (size_t)KQH * 256}, {&p->w3sq, (size_t)KQH * 256}};
-  p->has_std = 0;
-  for (auto& x : a)
-    if (hipMalloc((void**)x.q, x.n * 4) != hipSuccess) return pfail(ETG_ERR_ALLOC, "etg_policy_create: hipMalloc failed");
+  if (int rc = dev::alloc(policy_buffers(p), "etg_policy_create")) { etg_policy_destroy(p); return rc; }
   *out = p;
   return ETG_OK;
 }
@@ -426,8 +423,6 @@ extern "C" int etg_policy_sample(EtgPolicy* p, const float* obs, int n, const fl
 extern "C" void etg_policy_destroy(EtgPolicy* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
-  float* ptrs[] = {p->w1, p->b1, p->w2, p->b2, p->w3, p->b3, p->w3s, p->b3s, p->w1h, p->w2h, p->w3h, p->w3sh, p->w12q, p->w3q, p->w3sq};
-  for (float* q : ptrs)
-    if (q) (void)hipFree(q);
+  dev::release(policy_buffers(p));
   delete p;
 }

@@ -260,6 +260,57 @@ def test_transplant_from_the_16_lane_to_the_4_lane_mapping_matches_the_oracle():
     dst.close()
 
 
+# The record layout is part of the snapshot format.  Both figures depend on compile-time layout constants only, so one pair
+# serves every configuration; recorded from the library before the handle's arrays moved into one table
+# (profiles/handle_arrays_isa_identity.txt: tests/golden/make_golden_snapshot.py prints them).
+PARENT_ROW_BYTES = 20288
+PARENT_LAYOUT_FP = 0x77F71B8C95663636
+
+
+@pytest.mark.parametrize("lanes", [16, 4])
+def test_record_layout_is_the_recorded_one(lanes):
+    _need_gpu()
+    env = _make(16, lanes_per_robot=lanes)
+    env.reset()
+    hdr = env.snapshot().header
+    assert int(hdr.row_bytes) == PARENT_ROW_BYTES == int(env._lib.etg_snapshot_row_bytes(env._h))
+    assert int(hdr.layout_fp) == PARENT_LAYOUT_FP
+    env.close()
+
+
+def test_records_of_the_parent_library_continue_bit_for_bit():
+    """layout_fp hashes the segments' shapes and places, not which array a segment belongs to, and a round trip within one
+    library cannot see two arrays of equal shape swapped on both sides.  tests/golden/snapshot_parent.npz holds two records
+    that the library before the array table saved (tests/golden/make_golden_snapshot.py; next-episode rows pending, so every
+    segment is live) and what those two robots did on the next 3 zero-action steps, on a 4th that ends their episodes (the
+    restart reads the settle cache and takes the prepared rows) and on 2 steps of the new episodes.  The device code is the same
+    and a robot's step depends on its own state only, so the restored robots repeat the rows bit for bit."""
+    _need_gpu()
+    import ctypes
+    import json
+    import os
+    from paddlerobotics_amd import _lib
+    from paddlerobotics_amd.env import EnvSnapshot, make_env
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "snapshot_parent.npz"))
+    kw = json.loads(str(g["env"]))
+    hdr = _lib.EtgSnapshotHeader.from_buffer_copy(g["header"].tobytes())
+    assert ctypes.sizeof(hdr) == g["header"].size and hdr.next_dyn == 1 and hdr.n == 2
+    assert (int(hdr.row_bytes), int(hdr.layout_fp)) == (PARENT_ROW_BYTES, PARENT_LAYOUT_FP)
+    ids = [int(i) for i in g["env_ids"]]
+    assert ids == [3, 9]
+    env = make_env("Quadrupedal", device="cuda:0", **kw)
+    env.reset()
+    env.restore(EnvSnapshot(torch.as_tensor(g["rows"]).cuda().contiguous(), hdr, torch.as_tensor(g["env_ids"]).cuda()))
+    zero = torch.zeros(kw["num_envs"], 12, device="cuda:0")
+    assert g["obs"].shape[0] == 6 and not g["done"][:3].any() and g["done"][3].all() and not g["done"][4:].any()
+    for k in range(g["obs"].shape[0]):
+        obs, reward, done, _ = env.step(zero, donef=torch.as_tensor(g["donef"][k]).cuda())
+        for name, got in (("obs", obs), ("reward", reward), ("done", done)):
+            want = torch.as_tensor(g[name][k])
+            assert torch.equal(got[ids].cpu(), want), "%s of the restored robots differs at step %d" % (name, k)
+    env.close()
+
+
 def _refused(env, snap, ids):
     from paddlerobotics_amd._lib import EtgError
     before, lam = env.get_state(), env.get_contact_impulses()
