@@ -1,12 +1,15 @@
-"""ctypes binding of the C-ABI in include/etgsim.h, include/etgsim_step_policy.h, include/etgsim_terminal.h,
-include/etgsim_render.h, include/etgsim_sac.h, include/etgsim_bc.h, include/etgsim_snapshot.h, include/etgsim_collect.h, include/etgsim_monitor.h, include/etgsim_nstep.h, include/etgsim_heightscan.h and include/etgsim_ppo.h
-(paddlerobotics_amd/csrc/libetgsim.so).
+"""ctypes binding of the C-ABI (paddlerobotics_amd/csrc/libetgsim.so).  The prototypes are read from the headers under include/
+that build.HEADERS lists: a header is the only place where an entry point's parameters are written down.
 
 There is no CPU fallback: if the library is missing this module raises, and if no HIP
 device is visible etg_create() fails with ETG_ERR_NO_DEVICE.
 """
+import collections
 import ctypes as C
 import os
+import re
+
+import torch
 
 from . import build as _build
 
@@ -67,6 +70,70 @@ class EtgSnapshotHeader(C.Structure):
                 ("all_cached", C.c_uint8), ("strength_on", C.c_uint8), ("next_dyn", C.c_uint8), ("pad_", C.c_uint8 * 2)]
 
 
+# C types passed by value -> ctypes.  Every T* is a c_void_p and every T** a POINTER(c_void_p); anything else is refused.
+_CTYPES = {"int": C.c_int, "int32_t": C.c_int, "float": C.c_float, "double": C.c_double, "uint64_t": C.c_uint64,
+           "int64_t": C.c_longlong, "long long": C.c_longlong}
+# host out-parameters that the callers pass with byref(): {function: {parameter index: type}}
+_TYPED = {"etg_snapshot_save": {4: C.POINTER(EtgSnapshotHeader)}, "etg_snapshot_restore": {4: C.POINTER(EtgSnapshotHeader)},
+          "etg_rollout_wave_cycles": {3: C.POINTER(C.c_int), 4: C.POINTER(C.c_int)},
+          "etg_ppo2_get_state": {1: C.POINTER(C.c_double), 2: C.POINTER(C.c_int), 3: C.POINTER(C.c_longlong), 4: C.POINTER(C.c_double)}}
+_DECL = re.compile(r"([A-Za-z_][\w\s*]*?)\b(etg_[a-z0-9_]+)\s*\(([^;{}]*)\)\s*;")
+
+
+def _ctype(func, decl, param):
+    """ctypes type of `decl`: a parameter of `func` with its name (`param`), or its return type"""
+    m = re.fullmatch(r"\s*([\w\s]+?)\s*((?:\*\s*)*)" + (r"\b\w+\s*" if param else ""), re.sub(r"\bconst\b", " ", decl))
+    base, stars = (" ".join(m.group(1).split()), m.group(2).count("*")) if m else ("", 0)
+    if stars == 0 and base in _CTYPES:
+        return _CTYPES[base]
+    if stars == 0 and base == "void" and not param:
+        return None
+    if stars == 1 and base:
+        return C.c_char_p if base == "char" and not param else C.c_void_p
+    if stars == 2 and base:
+        return C.POINTER(C.c_void_p)
+    raise EtgError("paddlerobotics_amd: %s: no ctypes mapping for `%s`" % (func, " ".join(decl.split())))
+
+
+def parse_header(text):
+    """{name: (restype, argtypes)} of every etg_* declaration in the text of a C header.  A type outside the mapping above
+    (a struct by value, a function pointer, an array, a parameter without its name) and a declaration that this cannot
+    split raise EtgError: nothing is guessed and nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#(?:.*\\\n)*.*$", " ", text, flags=re.M)      # preprocessor lines, continued ones included
+    decls = _DECL.findall(text)
+    odd = collections.Counter(re.findall(r"\b(etg_[a-z0-9_]+)\s*\(", text)) - collections.Counter(name for _, name, _ in decls)
+    if odd:
+        raise EtgError("paddlerobotics_amd: cannot split the declaration of %s" % ", ".join(sorted(odd)))
+    out = {}
+    for ret, name, params in decls:
+        if name in out:
+            raise EtgError("paddlerobotics_amd: %s is declared twice" % name)
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (_ctype(name, ret, False), [_ctype(name, p, True) for p in params])
+        for i, t in _TYPED.get(name, {}).items():
+            if out[name][1][i] is not C.c_void_p:
+                raise EtgError("paddlerobotics_amd: %s: parameter %d is typed in _TYPED but is no pointer in the header" % (name, i))
+            out[name][1][i] = t
+    return out
+
+
+def prototypes():
+    """parse_header over the headers of include/, checked against the *_SYMBOLS lists above"""
+    out = {}
+    for h in _build.HEADERS:
+        path = os.path.normpath(os.path.join(_build.CSRC, h))
+        if os.path.basename(os.path.dirname(path)) == "include":
+            protos = parse_header(open(path).read())
+            if set(protos) & set(out):
+                raise EtgError("paddlerobotics_amd: %s: declared in another header too" % ", ".join(sorted(set(protos) & set(out))))
+            out.update(protos)
+    listed = {s for k, v in globals().items() if k.endswith("SYMBOLS") for s in v}
+    if listed != set(out):
+        raise EtgError("paddlerobotics_amd: the *_SYMBOLS lists and the headers differ: %s" % ", ".join(sorted(listed ^ set(out))))
+    return out
+
+
 def lib_path():
     # ETG_LIB selects an alternative build of the same HIP sources (A/B experiments in tools/)
     return os.environ.get("ETG_LIB", _build.LIB)
@@ -81,114 +148,12 @@ def load():
         raise EtgError(
             "paddlerobotics_amd: %s is missing -- build it with `python -m paddlerobotics_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
-    # torch first: its HIP runtime then satisfies the library's libamdhip64.so.7 / libhsa-runtime64.so.1 by soname.  Loaded the
-    # other way round, the process maps a second HIP + HSA stack, and whichever initialises second finds no device.
-    import torch  # noqa: F401
+    # torch first (imported above): its HIP runtime then satisfies the library's libamdhip64.so.7 / libhsa-runtime64.so.1 by
+    # soname.  Loaded the other way round, the process maps a second HIP + HSA stack, and whichever initialises second finds no device.
     lib = C.CDLL(path)
-    lib.etg_last_error.restype = C.c_char_p
-    vp, i32 = C.c_void_p, C.c_int
-    lib.etg_create.argtypes = [vp, vp, i32, C.POINTER(vp)]
-    lib.etg_destroy.argtypes = [vp]
-    lib.etg_destroy.restype = None
-    lib.etg_lanes_per_robot.argtypes = [vp]
-    lib.etg_set_params.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-    lib.etg_set_heightfield.argtypes = [vp, vp, vp]
-    lib.etg_set_external_force.argtypes = [vp, vp, vp]
-    lib.etg_set_motor_strength.argtypes = [vp, vp, vp, vp]
-    lib.etg_random_pushes.argtypes = [vp, C.c_uint64, C.c_float, i32, C.c_float, C.c_float, vp]
-    lib.etg_clear_pushes.argtypes = [vp, vp, vp]
-    lib.etg_set_reset_offsets.argtypes = [vp, vp, vp, vp]
-    lib.etg_set_sensor_noise.argtypes = [vp, vp, C.c_uint64]
-    lib.etg_reset.argtypes = [vp, vp, vp, vp]
-    lib.etg_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.etg_step_autoreset.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.etg_step_range.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.etg_episode_stats.argtypes = [vp, vp, vp, vp]
-    lib.etg_rollout_openloop.argtypes = [vp, i32, vp, vp, vp, vp]
-    lib.etg_get_state.argtypes = [vp, vp, vp]
-    lib.etg_set_state.argtypes = [vp, vp, vp]
-    lib.etg_set_rollout_mode.argtypes = [vp, i32]
-    lib.etg_rollout_wave_cycles.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32), vp]
-    lib.etg_get_contact_impulses.argtypes = [vp, vp, vp]
-    lib.etg_set_contact_impulses.argtypes = [vp, vp, vp]
-    lib.etg_leg_kinematics.argtypes = [vp, vp, i32, vp, vp, vp]
-    lib.etg_extra_sensors.argtypes = [vp, vp, vp, vp]
-    lib.etg_policy_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
-    lib.etg_policy_load.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.etg_policy_forward.argtypes = [vp, vp, i32, C.c_float, i32, vp, vp]
-    lib.etg_policy_load_std.argtypes = [vp, vp, vp, vp]
-    lib.etg_policy_sample.argtypes = [vp, vp, i32, vp, C.c_float, i32, vp, vp, vp]
-    lib.etg_policy_destroy.argtypes = [vp]
-    lib.etg_rollout_policy.argtypes = [vp, vp, i32, C.c_float, i32, i32, vp, vp, vp, vp]
-    lib.etg_rollout_policy_record.argtypes = [vp, vp, i32, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.etg_step_policy.argtypes = [vp, vp, C.c_float, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.etg_collect_policy.argtypes = [vp, vp, C.c_float, i32, i32, i32, i32] + [vp] * 12
-    lib.etg_collect_policy_info.argtypes = [vp, vp, C.c_float, i32, i32, i32, i32] + [vp] * 13
-    lib.etg_monitor_feed.argtypes = [i32, i32, i32, C.c_longlong, C.c_float, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
-    lib.etg_nstep_feed.argtypes = [i32, i32, i32, i32, C.c_float, i32, C.c_longlong, i32, i32] + [vp] * 18 + [C.c_longlong, vp, vp, vp]
-    lib.etg_nstep_flush.argtypes = [i32, i32, i32, C.c_float, i32, C.c_longlong, i32, i32] + [vp] * 11 + [C.c_longlong, vp, vp, vp]
-    lib.etg_scan_pose.argtypes = [vp, vp, vp]
-    lib.etg_height_scan_at.argtypes = [vp, vp, vp, i32, vp, i32, C.c_float, C.c_float, vp, vp]
-    lib.etg_height_scan.argtypes = [vp, vp, i32, C.c_float, C.c_float, vp, vp]
-    lib.etg_step_autoreset_terminal.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.etg_extra_sensors_terminal.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.etg_render.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp]
-    lib.etg_snapshot_row_bytes.argtypes = [vp]
-    lib.etg_snapshot_save.argtypes = [vp, vp, i32, vp, C.POINTER(EtgSnapshotHeader), vp]
-    lib.etg_snapshot_restore.argtypes = [vp, vp, i32, vp, C.POINTER(EtgSnapshotHeader), vp]
-    lib.etg_sac_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
-    lib.etg_sac_destroy.argtypes = [vp]
-    lib.etg_sac_set_hyper.argtypes = [vp] + [C.c_double] * 5
-    lib.etg_sac_load.argtypes = [vp, C.POINTER(vp), i32, vp]
-    lib.etg_sac_store.argtypes = [vp, C.POINTER(vp), i32, vp]
-    lib.etg_sac_load_opt.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.etg_sac_store_opt.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.etg_sac_learn.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    lib.etg_sac_learn_replay.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    lib.etg_sac_grads.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, C.POINTER(vp), vp]
-    lib.etg_sac_sync_policy.argtypes = [vp, vp, vp]
-    lib.etg_bc_create.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
-    lib.etg_bc_destroy.argtypes = [vp]
-    lib.etg_bc_set_hyper.argtypes = [vp, C.c_double, C.c_double]
-    lib.etg_bc_load.argtypes = [vp, C.POINTER(vp), i32, vp]
-    lib.etg_bc_store.argtypes = [vp, C.POINTER(vp), i32, vp]
-    lib.etg_bc_load_opt.argtypes = [vp, vp, vp, vp, vp]
-    lib.etg_bc_store_opt.argtypes = [vp, vp, vp, vp, vp]
-    lib.etg_bc_set_teacher.argtypes = [vp, C.POINTER(vp), vp]
-    lib.etg_bc_learn.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
-    lib.etg_bc_learn_replay.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    lib.etg_bc_grads.argtypes = [vp, vp, vp, i32, vp, vp, C.POINTER(vp), vp]
-    lib.etg_bc_sync_policy.argtypes = [vp, vp, vp]
-    lib.etg_ppo_create.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
-    lib.etg_ppo_destroy.argtypes = [vp]
-    lib.etg_ppo_set_hyper.argtypes = [vp] + [C.c_double] * 4
-    lib.etg_ppo_load.argtypes = [vp, C.POINTER(vp), i32, vp]
-    lib.etg_ppo_store.argtypes = [vp, C.POINTER(vp), i32, vp]
-    lib.etg_ppo_load_opt.argtypes = [vp, vp, vp, vp, vp]
-    lib.etg_ppo_store_opt.argtypes = [vp, vp, vp, vp, vp]
-    lib.etg_ppo_sync_policy.argtypes = [vp, vp, vp]
-    lib.etg_ppo_prepare.argtypes = [vp, vp, vp, vp, i32, vp]
-    lib.etg_ppo_gae.argtypes = [vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp]
-    lib.etg_ppo_norm_adv.argtypes = [vp, vp, i32, vp]
-    lib.etg_ppo_fetch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.etg_ppo_learn.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
-    lib.etg_ppo_learn_rows.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-    lib.etg_ppo_grads.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp), vp]
-    lib.etg_ppo2_set_controls.argtypes = [vp, C.c_double, C.c_double, C.c_double, i32, C.c_double, C.c_double]
-    lib.etg_ppo2_learn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]
-    lib.etg_ppo2_grads.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(vp), vp]
-    lib.etg_ppo2_reset_stop.argtypes = [vp, vp]
-    lib.etg_ppo2_set_state.argtypes = [vp, C.c_double, i32, vp]
-    lib.etg_ppo2_get_state.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_longlong), C.POINTER(C.c_double), vp]
-    lib.etg_rollout_actions.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.etg_prepare_next_dynamics.argtypes = [vp, vp, vp, vp]
-    lib.etg_next_dynamics_pending.argtypes = [vp, vp, vp]
-    lib.etg_policy_destroy.restype = None
-    dbl = C.c_double
-    lib.etg_fit_etg.argtypes = [vp, i32, vp, vp, dbl, dbl, dbl, dbl, dbl, i32, vp, vp, vp]
-    ll = C.c_longlong
-    lib.etg_replay_begin.argtypes = [vp, i32, ll, vp, vp, vp, i32, vp, i32, vp, vp, C.c_float, vp, vp]
-    lib.etg_replay_end.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    for name, (restype, argtypes) in prototypes().items():
+        f = getattr(lib, name)
+        f.restype, f.argtypes = restype, argtypes
     # a library built from another revision of include/etgsim.h would read past (or short of) the structs this binding
     # passes to etg_create: refuse it here, with the reason, instead of simulating with garbage parameters
     from . import a1_model as _A
@@ -207,3 +172,13 @@ ETG_ERR_STATE = -5   # include/etgsim.h
 def check(code):
     if code != 0:
         raise EtgError("etgsim error %d: %s" % (code, load().etg_last_error().decode()))
+
+
+def ptr(t):
+    """a tensor's device pointer as an argument (None stays None: an optional array)"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream_ptr(device):
+    """torch's current stream on `device` as the `void* stream` argument"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)

@@ -9,6 +9,8 @@ from collections import OrderedDict
 import torch
 import torch.nn.functional as F
 
+from ._lib import ptr as _ptr, stream_ptr
+
 LOG_SIG_MAX, LOG_SIG_MIN = 2.0, -20.0      # model/mujoco_model.py:21-22
 
 ACTOR_KEYS = ["actor_model.%s.%s" % (l, p) for l in ("l1", "l2", "mean_linear", "std_linear") for p in ("weight", "bias")]
@@ -39,10 +41,6 @@ def init_like_reference(obs_dim, action_dim=12, hidden=256, seed=0):
         sd[k] = (torch.rand(out, fan_in, generator=g) * 2 - 1) * bound
         sd[k[:-6] + "bias"] = (torch.rand(out, generator=g) * 2 - 1) * bound
     return sd
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def actor_forward(p, obs):
@@ -104,7 +102,7 @@ class ActorCriticLearner:
         return getattr(self._lib, "etg_%s_%s" % (self.PREFIX, name))
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream_ptr(self.device)
 
     def _set_hyper(self):
         self._check(self._c("set_hyper")(self._h, *[getattr(self, k) for k in self.HYPER]))

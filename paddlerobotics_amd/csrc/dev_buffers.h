@@ -1,5 +1,6 @@
 // dev_buffers.h -- a handle's device buffers as ONE list that its create, its destroy and whatever allocates later all walk:
-// a buffer entered in the list is allocated, zeroed and freed; nothing else has to be kept in step.  Host code only.
+// a buffer entered in the list is allocated, zeroed and freed; nothing else has to be kept in step.  And what the entry points
+// outside etg_kernels.hip share to refuse a call: fail, hip_fail, device_ptr.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -17,6 +18,18 @@ int fail(int code, const char* who, const char* what) {
   static thread_local char msg[200];
   snprintf(msg, sizeof msg, "%s: %s", who, what);
   return fail(code, msg);
+}
+int hip_fail(const char* who, hipError_t e) { return fail(ETG_ERR_HIP, who, hipGetErrorString(e)); }
+
+// Is p device memory?  If so its device becomes the current one: a launch goes to the device that owns the memory, and the
+// caller's current device may be another one.  The query alone is no proof -- it can succeed for a host pointer that was never
+// registered (type hipMemoryTypeUnregistered) -- so the type is required to be device memory.
+bool device_ptr(const void* p) {
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice &&
+      hipSetDevice(attr.device) == hipSuccess) return true;
+  (void)hipGetLastError();
+  return false;
 }
 
 // Allocates the buffers whose pointer is still null (all of them in a value-initialised handle), then zeroes every one: with

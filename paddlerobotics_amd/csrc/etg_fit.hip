@@ -10,9 +10,7 @@
 // 1.24 ms per 4096 candidates, 7 % of an ES generation.)
 #include <hip/hip_runtime.h>
 
-#include "../../include/etgsim.h"
-
-extern "C" void etg_set_last_error_(const char* msg);
+#include "dev_buffers.h"
 
 namespace {
 constexpr int H = ETG_RBF_H, NP = 6;
@@ -85,26 +83,11 @@ __global__ void __launch_bounds__(64) k_etg_fit(const double* __restrict__ pts, 
 extern "C" int etg_fit_etg(const double* points, int nb, const double* feats, const double* w0, double b0x, double b0z,
                            double precision, double alpha, double lamb, int max_iter, double* out_w, double* out_b,
                            void* stream) {
-  if (!points || !feats || !w0 || !out_w || !out_b || nb <= 0 || max_iter < 0) {
-    etg_set_last_error_("etg_fit_etg: bad arguments");
-    return ETG_ERR_BAD_ARG;
-  }
-  // launch on the device that owns the buffers (the caller's current device may be another one): the other entry
-  // points bind their handle's device the same way.  The query alone is no proof: it can succeed for a host pointer that was
-  // never registered (type hipMemoryTypeUnregistered), so the type is required to be device memory
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, points) != hipSuccess || attr.type != hipMemoryTypeDevice ||
-      hipSetDevice(attr.device) != hipSuccess) {
-    (void)hipGetLastError();
-    etg_set_last_error_("etg_fit_etg: points is not a device pointer");
-    return ETG_ERR_BAD_ARG;
-  }
+  if (!points || !feats || !w0 || !out_w || !out_b || nb <= 0 || max_iter < 0) return dev::fail(ETG_ERR_BAD_ARG, "etg_fit_etg: bad arguments");
+  // launch on the device that owns the buffers: the other entry points bind their handle's device the same way
+  if (!dev::device_ptr(points)) return dev::fail(ETG_ERR_BAD_ARG, "etg_fit_etg: points is not a device pointer");
   const int threads = 8 * nb;   // a quad per (candidate, dimension)
   hipLaunchKernelGGL(k_etg_fit, dim3((threads + 63) / 64), dim3(64), 0, (hipStream_t)stream, points, feats, w0, b0x, b0z,
                      precision, alpha, lamb, max_iter, nb, out_w, out_b);
-  if (hipGetLastError() != hipSuccess) {
-    etg_set_last_error_("etg_fit_etg: launch failed");
-    return ETG_ERR_HIP;
-  }
-  return ETG_OK;
+  return hipGetLastError() == hipSuccess ? ETG_OK : dev::fail(ETG_ERR_HIP, "etg_fit_etg: launch failed");
 }

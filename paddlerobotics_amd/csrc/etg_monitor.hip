@@ -17,11 +17,9 @@
 // left in scratch: the feed kernel's first wave writes the new count while other waves may still be starting.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/etgsim_monitor.h"
-
-extern "C" void etg_set_last_error_(const char* msg);
+#include "dev_buffers.h"
 
 namespace {
 
@@ -144,24 +142,21 @@ __global__ void __launch_bounds__(FEED_BLOCK) k_monitor_feed(int n, int n_steps,
   running[(size_t)i * ETG_MON_DIM + f] = acc;
 }
 
-int fail(const char* msg) {
-  etg_set_last_error_(msg);
-  return ETG_ERR_BAD_ARG;
-}
-
 }  // namespace
+
+using dev::fail;
 
 extern "C" int etg_monitor_feed(int device, int num_envs, int n_steps, int64_t step0, float success_velx, const float* reward,
                                 const uint8_t* done, const float* info, float* running, float* records, int32_t* meta, int capacity,
                                 int64_t* count, int32_t* scratch, void* stream) {
-  if (num_envs < 1) return fail("etg_monitor_feed: num_envs must be at least 1");
-  if (n_steps < 1) return fail("etg_monitor_feed: n_steps must be at least 1");
-  if (capacity < 1) return fail("etg_monitor_feed: capacity must be at least 1");
-  if ((long long)num_envs * n_steps > 0x7fffffffll) return fail("etg_monitor_feed: num_envs * n_steps must be below 2^31");
-  if (!reward || !done || !info) return fail("etg_monitor_feed: reward, done and info must be non-null");
-  if (!running || !records || !meta) return fail("etg_monitor_feed: running, records and meta must be non-null");
-  if (!count || !scratch) return fail("etg_monitor_feed: count and scratch must be non-null");
-  if (device < 0) return fail("etg_monitor_feed: device must not be negative");
+  if (num_envs < 1) return fail(ETG_ERR_BAD_ARG, "etg_monitor_feed: num_envs must be at least 1");
+  if (n_steps < 1) return fail(ETG_ERR_BAD_ARG, "etg_monitor_feed: n_steps must be at least 1");
+  if (capacity < 1) return fail(ETG_ERR_BAD_ARG, "etg_monitor_feed: capacity must be at least 1");
+  if ((long long)num_envs * n_steps > 0x7fffffffll) return fail(ETG_ERR_BAD_ARG, "etg_monitor_feed: num_envs * n_steps must be below 2^31");
+  if (!reward || !done || !info) return fail(ETG_ERR_BAD_ARG, "etg_monitor_feed: reward, done and info must be non-null");
+  if (!running || !records || !meta) return fail(ETG_ERR_BAD_ARG, "etg_monitor_feed: running, records and meta must be non-null");
+  if (!count || !scratch) return fail(ETG_ERR_BAD_ARG, "etg_monitor_feed: count and scratch must be non-null");
+  if (device < 0) return fail(ETG_ERR_BAD_ARG, "etg_monitor_feed: device must not be negative");
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) {
     hipStream_t s = (hipStream_t)stream;
@@ -173,11 +168,5 @@ extern "C" int etg_monitor_feed(int device, int num_envs, int n_steps, int64_t s
                        (const int*)scratch);
     e = hipGetLastError();
   }
-  if (e != hipSuccess) {
-    static thread_local char buf[256];
-    snprintf(buf, sizeof(buf), "etg_monitor_feed: %s", hipGetErrorString(e));
-    etg_set_last_error_(buf);
-    return ETG_ERR_HIP;
-  }
-  return ETG_OK;
+  return e == hipSuccess ? ETG_OK : dev::hip_fail("etg_monitor_feed", e);
 }

@@ -20,11 +20,9 @@
 // is the same scan and rows kernels over one virtual step whose rows all come from the ring, and a one-wave pos_count update.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/etgsim_nstep.h"
-
-extern "C" void etg_set_last_error_(const char* msg);
+#include "dev_buffers.h"
 
 namespace {
 
@@ -227,21 +225,11 @@ __global__ void __launch_bounds__(ROW_BLOCK) k_nstep_tail(Args a, int keep) {
 
 __global__ void __launch_bounds__(64) k_nstep_advance(Args a) { advance(a, a.scratch[0], threadIdx.x); }
 
-int fail(const char* msg) {
-  etg_set_last_error_(msg);
-  return ETG_ERR_BAD_ARG;
-}
-
-int hip_fail(const char* who, hipError_t e) {
-  static thread_local char buf[256];
-  snprintf(buf, sizeof(buf), "%s: %s", who, hipGetErrorString(e));
-  etg_set_last_error_(buf);
-  return ETG_ERR_HIP;
-}
-
 unsigned row_blocks(long long waves) { return (unsigned)((waves + ROW_WAVES - 1) / ROW_WAVES); }
 
 }  // namespace
+
+using dev::fail;
 
 extern "C" int etg_nstep_feed(int device, int num_envs, int n_steps, int n, float gamma, int hist, int64_t step0, int obs_dim,
                               int act_dim, const float* rec_obs, const float* rec_action, const float* rec_reward,
@@ -250,22 +238,22 @@ extern "C" int etg_nstep_feed(int device, int num_envs, int n_steps, int n, floa
                               float* tail_next_obs, float* tail_terminal, int32_t* pending, float* mem_obs, float* mem_action,
                               float* mem_reward, float* mem_next_obs, float* mem_terminal, int64_t max_size, int64_t* pos_count,
                               int32_t* scratch, void* stream) {
-  if (num_envs < 1) return fail("etg_nstep_feed: num_envs must be at least 1");
-  if (n_steps < 1) return fail("etg_nstep_feed: n_steps must be at least 1");
-  if (n < 1 || n > ETG_NSTEP_MAX_N) return fail("etg_nstep_feed: n must be 1..16");
-  if (hist < 0 || hist > n - 1) return fail("etg_nstep_feed: hist must be 0..n-1");
-  if (step0 < hist) return fail("etg_nstep_feed: step0 must be at least hist");
-  if (obs_dim < 1 || act_dim < 1) return fail("etg_nstep_feed: obs_dim and act_dim must be at least 1");
+  if (num_envs < 1) return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: num_envs must be at least 1");
+  if (n_steps < 1) return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: n_steps must be at least 1");
+  if (n < 1 || n > ETG_NSTEP_MAX_N) return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: n must be 1..16");
+  if (hist < 0 || hist > n - 1) return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: hist must be 0..n-1");
+  if (step0 < hist) return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: step0 must be at least hist");
+  if (obs_dim < 1 || act_dim < 1) return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: obs_dim and act_dim must be at least 1");
   if (((long long)n_steps + n - 1) * num_envs > (long long)max_size)
-    return fail("etg_nstep_feed: (n_steps + n - 1) * num_envs rows must fit the memory (max_size)");
-  if ((long long)num_envs * ((long long)n_steps + n) > 0x7fffffffll) return fail("etg_nstep_feed: num_envs * (n_steps + n) must be below 2^31");
+    return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: (n_steps + n - 1) * num_envs rows must fit the memory (max_size)");
+  if ((long long)num_envs * ((long long)n_steps + n) > 0x7fffffffll) return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: num_envs * (n_steps + n) must be below 2^31");
   if (!rec_obs || !rec_action || !rec_reward || !rec_done || !rec_next_obs || !rec_terminal || !rec_ep_len)
-    return fail("etg_nstep_feed: the seven record arrays must be non-null");
+    return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: the seven record arrays must be non-null");
   if (!hist_obs || !hist_action || !hist_reward || !tail_next_obs || !tail_terminal || !pending)
-    return fail("etg_nstep_feed: the history ring, the tail and pending must be non-null");
+    return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: the history ring, the tail and pending must be non-null");
   if (!mem_obs || !mem_action || !mem_reward || !mem_next_obs || !mem_terminal || !pos_count || !scratch)
-    return fail("etg_nstep_feed: the memory's arrays, pos_count and scratch must be non-null");
-  if (device < 0) return fail("etg_nstep_feed: device must not be negative");
+    return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: the memory's arrays, pos_count and scratch must be non-null");
+  if (device < 0) return fail(ETG_ERR_BAD_ARG, "etg_nstep_feed: device must not be negative");
   Args a{num_envs, n_steps, n, hist, obs_dim, act_dim, n > 1 ? (int)(step0 % (n - 1)) : 0, gamma, (long long)max_size, rec_obs, rec_action, rec_reward,
          rec_next_obs, rec_terminal, rec_done, (const int*)rec_ep_len, hist_obs, hist_action, hist_reward, tail_next_obs, tail_terminal,
          (int*)pending, mem_obs, mem_action, mem_reward, mem_next_obs, mem_terminal, (long long*)pos_count, (int*)scratch};
@@ -278,7 +266,7 @@ extern "C" int etg_nstep_feed(int device, int num_envs, int n_steps, int n, floa
     hipLaunchKernelGGL(k_nstep_tail, dim3(row_blocks((long long)(keep + 1) * num_envs)), dim3(ROW_BLOCK), 0, s, a, keep);
     e = hipGetLastError();
   }
-  return e == hipSuccess ? ETG_OK : hip_fail("etg_nstep_feed", e);
+  return e == hipSuccess ? ETG_OK : dev::hip_fail("etg_nstep_feed", e);
 }
 
 extern "C" int etg_nstep_flush(int device, int num_envs, int n, float gamma, int hist, int64_t step0, int obs_dim, int act_dim,
@@ -286,19 +274,19 @@ extern "C" int etg_nstep_flush(int device, int num_envs, int n, float gamma, int
                                const float* tail_terminal, int32_t* pending, float* mem_obs, float* mem_action, float* mem_reward,
                                float* mem_next_obs, float* mem_terminal, int64_t max_size, int64_t* pos_count, int32_t* scratch,
                                void* stream) {
-  if (num_envs < 1) return fail("etg_nstep_flush: num_envs must be at least 1");
-  if (n < 1 || n > ETG_NSTEP_MAX_N) return fail("etg_nstep_flush: n must be 1..16");
-  if (hist < 0 || hist > n - 1) return fail("etg_nstep_flush: hist must be 0..n-1");
-  if (step0 < hist) return fail("etg_nstep_flush: step0 must be at least hist");
-  if (obs_dim < 1 || act_dim < 1) return fail("etg_nstep_flush: obs_dim and act_dim must be at least 1");
-  if ((long long)(n - 1) * num_envs > (long long)max_size) return fail("etg_nstep_flush: (n - 1) * num_envs rows must fit the memory (max_size)");
-  if (max_size < 1) return fail("etg_nstep_flush: max_size must be at least 1");
-  if ((long long)num_envs * n > 0x7fffffffll) return fail("etg_nstep_flush: num_envs * n must be below 2^31");
+  if (num_envs < 1) return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: num_envs must be at least 1");
+  if (n < 1 || n > ETG_NSTEP_MAX_N) return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: n must be 1..16");
+  if (hist < 0 || hist > n - 1) return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: hist must be 0..n-1");
+  if (step0 < hist) return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: step0 must be at least hist");
+  if (obs_dim < 1 || act_dim < 1) return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: obs_dim and act_dim must be at least 1");
+  if ((long long)(n - 1) * num_envs > (long long)max_size) return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: (n - 1) * num_envs rows must fit the memory (max_size)");
+  if (max_size < 1) return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: max_size must be at least 1");
+  if ((long long)num_envs * n > 0x7fffffffll) return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: num_envs * n must be below 2^31");
   if (!hist_obs || !hist_action || !hist_reward || !tail_next_obs || !tail_terminal || !pending)
-    return fail("etg_nstep_flush: the history ring, the tail and pending must be non-null");
+    return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: the history ring, the tail and pending must be non-null");
   if (!mem_obs || !mem_action || !mem_reward || !mem_next_obs || !mem_terminal || !pos_count || !scratch)
-    return fail("etg_nstep_flush: the memory's arrays, pos_count and scratch must be non-null");
-  if (device < 0) return fail("etg_nstep_flush: device must not be negative");
+    return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: the memory's arrays, pos_count and scratch must be non-null");
+  if (device < 0) return fail(ETG_ERR_BAD_ARG, "etg_nstep_flush: device must not be negative");
   Args a{num_envs, 1, n, hist, obs_dim, act_dim, n > 1 ? (int)(step0 % (n - 1)) : 0, gamma, (long long)max_size, nullptr, nullptr, nullptr, nullptr, nullptr,
          nullptr, nullptr, (float*)hist_obs, (float*)hist_action, (float*)hist_reward, (float*)tail_next_obs, (float*)tail_terminal,
          (int*)pending, mem_obs, mem_action, mem_reward, mem_next_obs, mem_terminal, (long long*)pos_count, (int*)scratch};
@@ -310,5 +298,5 @@ extern "C" int etg_nstep_flush(int device, int num_envs, int n, float gamma, int
     hipLaunchKernelGGL(k_nstep_advance, dim3(1), dim3(64), 0, s, a);
     e = hipGetLastError();
   }
-  return e == hipSuccess ? ETG_OK : hip_fail("etg_nstep_flush", e);
+  return e == hipSuccess ? ETG_OK : dev::hip_fail("etg_nstep_flush", e);
 }

@@ -16,11 +16,8 @@
 // and the transition count live in device memory.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
-#include "../../include/etgsim.h"
-
-extern "C" void etg_set_last_error_(const char* msg);
+#include "dev_buffers.h"
 
 namespace {
 
@@ -218,36 +215,16 @@ __global__ void k_replay_end_rows(const int* __restrict__ slot, int n, const flo
   }
 }
 
-int fail(const char* msg) {
-  etg_set_last_error_(msg);
-  return ETG_ERR_BAD_ARG;
-}
-// launch on the device that owns the memory (the caller's current device may be another one).  The query can succeed for a
-// host pointer that was never registered (type hipMemoryTypeUnregistered): only device memory is accepted
-bool bind_device(const void* p) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice &&
-      hipSetDevice(attr.device) == hipSuccess) return true;
-  (void)hipGetLastError();
-  return false;
-}
-int hip_fail(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return ETG_OK;
-  static thread_local char buf[256];
-  snprintf(buf, sizeof(buf), "%s: %s", what, hipGetErrorString(e));
-  etg_set_last_error_(buf);
-  return ETG_ERR_HIP;
-}
-
 }  // namespace
+
+using dev::fail;
 
 extern "C" int etg_replay_begin(const uint8_t* alive, int n, long long max_size, long long* pos_count, int32_t* slot,
                                 const float* obs, int obs_dim, const float* act, int act_dim, float* mem_obs, float* mem_act,
                                 float act_scale, float* act_scaled, void* stream) {
   if (n <= 0 || max_size <= 0 || n > max_size || !pos_count || !slot || !obs || !act || !mem_obs || !mem_act || obs_dim <= 0 || act_dim <= 0)
-    return fail("etg_replay_begin: bad arguments (a batch must fit the memory)");
-  if (!bind_device(mem_obs)) return fail("etg_replay_begin: mem_obs is not a device pointer");
+    return fail(ETG_ERR_BAD_ARG, "etg_replay_begin: bad arguments (a batch must fit the memory)");
+  if (!dev::device_ptr(mem_obs)) return fail(ETG_ERR_BAD_ARG, "etg_replay_begin: mem_obs is not a device pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n <= 8192) {
     hipLaunchKernelGGL(k_replay_slots, dim3(1), dim3(1024), 0, s, alive, n, max_size, pos_count, slot);
@@ -265,16 +242,17 @@ extern "C" int etg_replay_begin(const uint8_t* alive, int n, long long max_size,
     hipLaunchKernelGGL(k_replay_begin_rows<false>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, slot, n, obs, obs_dim, mem_obs, act,
                        act_dim, mem_act, act_scale, act_scaled);
   }
-  return hip_fail("etg_replay_begin");
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ETG_OK : dev::hip_fail("etg_replay_begin", e);
 }
 
 extern "C" int etg_replay_end(const int32_t* slot, int n, const float* reward, const uint8_t* done, const float* next_obs, int obs_dim,
                               float* mem_reward, float* mem_terminal, float* mem_next_obs, const float* info, int info_dim,
                               int n_sum, int velx_col, float* info_sum, uint8_t* alive, void* stream) {
   if (n <= 0 || !slot || !reward || !done || !next_obs || !mem_reward || !mem_terminal || !mem_next_obs || obs_dim <= 0)
-    return fail("etg_replay_end: bad arguments");
-  if (info && (info_dim <= 0 || n_sum < 0 || n_sum > info_dim || velx_col >= info_dim)) return fail("etg_replay_end: bad info layout");
-  if (!bind_device(mem_next_obs)) return fail("etg_replay_end: mem_next_obs is not a device pointer");
+    return fail(ETG_ERR_BAD_ARG, "etg_replay_end: bad arguments");
+  if (info && (info_dim <= 0 || n_sum < 0 || n_sum > info_dim || velx_col >= info_dim)) return fail(ETG_ERR_BAD_ARG, "etg_replay_end: bad info layout");
+  if (!dev::device_ptr(mem_next_obs)) return fail(ETG_ERR_BAD_ARG, "etg_replay_end: mem_next_obs is not a device pointer");
   hipStream_t s = (hipStream_t)stream;
   if (obs_dim <= 64) {
     hipLaunchKernelGGL(k_replay_end_rows<true>, dim3((unsigned)(n <= BIG_BATCH ? (n + 3) / 4 : 2048)), dim3(256), 0, s, slot, n, next_obs, obs_dim, mem_next_obs, reward,
@@ -284,5 +262,6 @@ extern "C" int etg_replay_end(const int32_t* slot, int n, const float* reward, c
     hipLaunchKernelGGL(k_replay_end_rows<false>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, slot, n, next_obs, obs_dim, mem_next_obs,
                        reward, done, mem_reward, mem_terminal, info, info_dim, n_sum, velx_col, info_sum, alive);
   }
-  return hip_fail("etg_replay_end");
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ETG_OK : dev::hip_fail("etg_replay_end", e);
 }

@@ -21,6 +21,7 @@ import torch
 
 from . import a1_model as A
 from . import _lib
+from ._lib import ptr as _ptr
 from . import heightscan as _hs
 from .etg import ETG_layer, Opt_with_points
 from .terrain import TERRAIN_TASKS, make_task_heightfield
@@ -93,10 +94,6 @@ class Box:
 
     def sample(self):
         return np.random.uniform(self.low, self.high).astype(self.dtype)
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class _InfoView(dict):
@@ -363,7 +360,7 @@ class BatchedQuadrupedEnv:
 
     # ---- plumbing --------------------------------------------------------------
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream_ptr(self.device)
 
     def _f32(self, x, shape, what):
         t = torch.as_tensor(x, dtype=torch.float32, device=self.device).contiguous()

@@ -67,7 +67,6 @@ def opt_with_points_batched(ETG, ETG_T, points, b0, w0, precision=1e-4, lamb=0.5
 
 def _fit_hip(pts, feats, b0, w0, precision, lamb, alpha=0.05, max_iter=1000):
     """The HIP kernel behind the C-ABI (csrc/etg_fit.hip: one lane per candidate-dimension)."""
-    import ctypes as C
     from . import _lib
     lib = _lib.load()
     dev = pts.device
@@ -77,8 +76,7 @@ def _fit_hip(pts, feats, b0, w0, precision, lamb, alpha=0.05, max_iter=1000):
     nb = pts.shape[0]
     w = torch.empty(nb, 3, feats.shape[1], dtype=torch.float64, device=dev)
     b = torch.empty(nb, 3, dtype=torch.float64, device=dev)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(lib.etg_fit_etg(C.c_void_p(pts.data_ptr()), nb, C.c_void_p(feats.data_ptr()), C.c_void_p(w0t.data_ptr()),
+    _lib.check(lib.etg_fit_etg(_lib.ptr(pts), nb, _lib.ptr(feats), _lib.ptr(w0t),
                                float(b0[0]), float(b0[-1]), float(precision), float(alpha), float(lamb), int(max_iter),
-                               C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), stream))
+                               _lib.ptr(w), _lib.ptr(b), _lib.stream_ptr(dev)))
     return w, b

@@ -25,14 +25,12 @@ import ctypes as C
 
 import torch
 
+from ._lib import ptr as _ptr, stream_ptr as _stream
+
 MON_DIM = 16
 RET, LEN, TERMS, SUCCESS, ENERGY, SWEEPS, X_END = 0, 1, 2, 9, 10, 11, 12
 TERM_KEYS = ("torso", "feet", "up", "tau", "stand", "badfoot", "footcontact")      # info columns 0..6 (a1_model.REWARD_KEYS)
 INFO_DIM, INFO_VELX, INFO_BASE, INFO_ENERGY, INFO_SWEEPS = 64, 8, 55, 61, 63          # include/etgsim.h ETG_INFO_*
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def scratch_ints(num_envs, n_steps):
@@ -78,7 +76,7 @@ class EpisodeMonitor:
             need = scratch_ints(n, K)
             if self._scratch is None or self._scratch.numel() < need:
                 self._scratch = torch.zeros(need, dtype=torch.int32, device=self.device)
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            stream = _stream(self.device)
             self._check(self._lib.etg_monitor_feed(self.device.index or 0, n, K, self.steps, C.c_float(self.success_velx), _ptr(reward),
                                                    _ptr(done), _ptr(info), _ptr(self.running), _ptr(self._records), _ptr(self._meta),
                                                    self.capacity, _ptr(self.count), _ptr(self._scratch), stream))

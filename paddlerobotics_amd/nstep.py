@@ -33,11 +33,9 @@ import ctypes as C
 import numpy as np
 import torch
 
+from ._lib import ptr as _ptr, stream_ptr as _stream
+
 MAX_N = 16                                     # include/etgsim_nstep.h: ETG_NSTEP_MAX_N
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def scratch_ints(num_envs, n_steps):
@@ -103,9 +101,6 @@ class NStepWriter:
                     self._feed_torch(*[x[s] for x in part])
             self.steps += k1 - k0
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _need_scratch(self, ints):
         if self._scratch is None or self._scratch.numel() < ints:
             self._scratch = torch.zeros(ints, dtype=torch.int32, device=self.device)
@@ -122,7 +117,7 @@ class NStepWriter:
         scratch = self._need_scratch(scratch_ints(self.num_envs, K))
         self._check(self._lib.etg_nstep_feed(self.device.index or 0, self.num_envs, K, self.n, C.c_float(self.gamma), min(self.t, self.n - 1),
                                              self.t, r.obs_dim, r.act_dim, _ptr(obs), _ptr(action), _ptr(reward), _ptr(done), _ptr(next_obs),
-                                             _ptr(terminal), _ptr(ep_len), *state, *mem, r.max_size, _ptr(r._pc), _ptr(scratch), self._stream()))
+                                             _ptr(terminal), _ptr(ep_len), *state, *mem, r.max_size, _ptr(r._pc), _ptr(scratch), _stream(self.device)))
         self.t += K
 
     def _chain(self, rewards):
@@ -182,7 +177,7 @@ class NStepWriter:
             state, mem = self._state_ptrs()
             scratch = self._need_scratch(scratch_ints(self.num_envs, 1))
             self._check(self._lib.etg_nstep_flush(self.device.index or 0, self.num_envs, n, C.c_float(self.gamma), back, t, r.obs_dim,
-                                                  r.act_dim, *state, *mem, r.max_size, _ptr(r._pc), _ptr(scratch), self._stream()))
+                                                  r.act_dim, *state, *mem, r.max_size, _ptr(r._pc), _ptr(scratch), _stream(self.device)))
         elif back > 0:
             H = n - 1
             ring = [(t - 1 - j) % H for j in range(back)]         # step t - 1 - j

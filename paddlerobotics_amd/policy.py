@@ -10,10 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
+from ._lib import ptr as _ptr, stream_ptr as _stream
 
 
 class MfmaPolicy:
@@ -54,7 +51,7 @@ class MfmaPolicy:
             ws.append(torch.as_tensor(t, dtype=torch.float32).to(self.device).contiguous())
         if tuple(ws[0].shape) != (self.hidden, self.obs_dim) or tuple(ws[4].shape) != (self.action_dim, self.hidden):
             raise ValueError("state_dict shapes do not match the policy dimensions")
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _stream(self.device)
         _lib.check(self._lib.etg_policy_load(self._h, *[_ptr(w) for w in ws], stream))
         self._w = ws
         self._std = None
@@ -83,7 +80,7 @@ class MfmaPolicy:
             raise ValueError("obs must be float32 [N,%d]" % self.obs_dim)
         if out is None:
             out = torch.empty(obs.shape[0], self.action_dim, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _stream(self.device)
         _lib.check(self._lib.etg_policy_forward(self._h, _ptr(obs), int(obs.shape[0]), C.c_float(act_scale),
                                                 int(precision), _ptr(out), stream))
         return out
@@ -102,7 +99,7 @@ class MfmaPolicy:
         noise = noise.to(torch.float32).contiguous()
         act = torch.empty(n, self.action_dim, device=self.device)
         logp = torch.empty(n, device=self.device) if return_logp else None
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _stream(self.device)
         _lib.check(self._lib.etg_policy_sample(self._h, _ptr(obs), n, _ptr(noise), C.c_float(act_scale), int(precision),
                                                _ptr(act), None if logp is None else _ptr(logp), stream))
         return (act, logp.unsqueeze(1)) if return_logp else act

@@ -22,9 +22,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from ._lib import ptr as _ptr, stream_ptr as _stream
 
 
 class DeviceReplayMemory:
@@ -59,9 +57,6 @@ class DeviceReplayMemory:
     def _count(self, v):
         self._pc[1] = v
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     # ---- fused path (HIP device): alive = uint8 [n] device tensor (or None); returns the int32 slot tensor
     def begin(self, obs, action, alive=None, act_scale=1.0, act_scaled=None):
         obs, action = self._rows(obs, self.obs_dim).contiguous(), self._rows(action, self.act_dim).contiguous()
@@ -71,7 +66,7 @@ class DeviceReplayMemory:
         slot = torch.empty(n, dtype=torch.int32, device=self.device)
         self._check(self._lib.etg_replay_begin(_ptr(alive), n, self.max_size, _ptr(self._pc), _ptr(slot), _ptr(obs), self.obs_dim,
                                                _ptr(action), self.act_dim, _ptr(self.obs), _ptr(self.action), C.c_float(act_scale),
-                                               _ptr(act_scaled), self._stream()))
+                                               _ptr(act_scaled), _stream(self.device)))
         return slot
 
     def end(self, slot, reward, done, next_obs, info_buf=None, n_sum=0, velx_col=-1, info_sum=None, alive=None):
@@ -85,7 +80,7 @@ class DeviceReplayMemory:
         info_dim = 0 if info_buf is None else int(info_buf.shape[1])
         self._check(self._lib.etg_replay_end(_ptr(slot), n, _ptr(reward), _ptr(done), _ptr(next_obs), self.obs_dim, _ptr(self.reward),
                                              _ptr(self.terminal), _ptr(self.next_obs), _ptr(info_buf), info_dim, int(n_sum), int(velx_col),
-                                             _ptr(info_sum), _ptr(alive), self._stream()))
+                                             _ptr(info_sum), _ptr(alive), _stream(self.device)))
 
     # ---- writing
     def slots(self, n, mask=None):
