@@ -15,8 +15,8 @@ is consumed by the iteration that collected it.
 evaluation line is followed by the per-episode log values (episode_reward, episode_step, the reward terms, success_rate) averaged
 over the training episodes that finished since the previous one.  With --checkpoint the monitor is saved (monitor.pt) and resumed.
 --height-scan: a perceptive learner -- the envs are made with sensor_mode={"height_scan": 1} on --task (default then
-"stairstair"), and DevicePPO learns on 49 + 15 = 64 columns.  The one-launch collection does not compute these columns, so
-collect_rollout takes its stepping path.
+"stairstair"), and DevicePPO learns on 49 + 15 = 64 columns.  The envs' height_scan dict has fused=True: the one-launch
+collection computes the columns itself, so collect_rollout keeps its one launch per rollout.
 --max-grad-norm / --clip-value / --target-kl: DevicePPO's controls (off by default) -- gradient-norm clipping per optimizer, PPO2's
 clipped value loss, and with --target-kl either early stopping of the iteration's updates (--kl-control stop, the default) or a
 KL-adaptive learning rate (adaptive).  All of it is decided on the device; the evaluation line then also prints lr_scale and
@@ -87,6 +87,7 @@ def main():
     kw = {"task": args.task or ("stairstair" if args.height_scan else "ground")}
     if args.height_scan:
         kw["sensor_mode"] = {"height_scan": 1}
+        kw["height_scan"] = {"fused": True}
     env = make_env("Quadrupedal", num_envs=args.num_envs, device=args.device, auto_reset=True, **kw)
     evl = make_env("Quadrupedal", num_envs=min(args.num_envs, 256), device=args.device, **kw)
     obs_dim, act_dim = env.observation_space.shape[0], env.action_space.shape[0]

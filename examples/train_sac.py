@@ -20,8 +20,9 @@ monitor is saved (monitor.pt) and resumed too.
 observation N steps later, terminal * gamma^(N-1)), so that one update carries reward N control steps back; 1 (the default)
 takes the 1-step path as it was.  With --checkpoint the writer is saved (nstep.pt) and resumed too.
 --height-scan: a perceptive learner -- the envs are made with sensor_mode={"height_scan": 1} (the default 5 x 3 grid of terrain
-clearances, heightscan.py) on --task (default then "stairstair"), and DeviceSAC learns on 49 + 15 = 64 columns.  The fused
-collection kernels do not compute these columns, so collect_continuous takes its stepping path."""
+clearances, heightscan.py) on --task (default then "stairstair"), and DeviceSAC learns on 49 + 15 = 64 columns.  The envs'
+height_scan dict has fused=True: the collection launches compute the columns themselves, so collect_continuous keeps its one
+launch per step or per chunk."""
 import argparse
 import os
 import sys
@@ -85,6 +86,7 @@ def main():
     kw = {"task": args.task or ("stairstair" if args.height_scan else "ground")}
     if args.height_scan:
         kw["sensor_mode"] = {"height_scan": 1}
+        kw["height_scan"] = {"fused": True}
     env = make_env("Quadrupedal", num_envs=args.num_envs, device=args.device, auto_reset=True, **kw)
     evl = make_env("Quadrupedal", num_envs=min(args.num_envs, 256), device=args.device, **kw)
     obs_dim, act_dim = env.observation_space.shape[0], env.action_space.shape[0]

@@ -54,6 +54,8 @@ PPO_SYMBOLS = ["etg_ppo_create", "etg_ppo_destroy", "etg_ppo_set_hyper", "etg_pp
 # ... and its controls (the same header, "Controls"): a list of their own, the base list above stays as it is
 PPO_CONTROL_SYMBOLS = ["etg_ppo2_set_controls", "etg_ppo2_learn", "etg_ppo2_grads", "etg_ppo2_reset_stop", "etg_ppo2_set_state",
                        "etg_ppo2_get_state"]
+# ... and include/etgsim_scan_policy.h
+SCAN_POLICY_SYMBOLS = ["etg_step_policy_scan", "etg_collect_policy_scan"]
 ABI_VERSION = 2      # include/etgsim.h: etg_version()
 
 

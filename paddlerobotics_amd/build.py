@@ -15,7 +15,7 @@ HEADERS = ["etg_core.h", "etg_core16.h", "gram16.h", "etg_layout.h", "policy_cor
            os.path.join("..", "..", "include", "etgsim_bc.h"), os.path.join("..", "..", "include", "etgsim_snapshot.h"),
            os.path.join("..", "..", "include", "etgsim_collect.h"), os.path.join("..", "..", "include", "etgsim_monitor.h"),
            os.path.join("..", "..", "include", "etgsim_nstep.h"), os.path.join("..", "..", "include", "etgsim_heightscan.h"),
-           os.path.join("..", "..", "include", "etgsim_ppo.h")]
+           os.path.join("..", "..", "include", "etgsim_ppo.h"), os.path.join("..", "..", "include", "etgsim_scan_policy.h")]
 LIB = os.path.join(CSRC, "libetgsim.so")
 
 
@@ -53,6 +53,7 @@ def is_stale():
 
 
 TU_PARTS = 8          # etg_kernels.hip: part 0 = host side + small kernels, parts 1..7 = the tick kernels' instantiations
+SCAN_PARTS = 3        # ... and parts 8..10 = the closed-loop kernels with the height scan (slots 8..10 of the table), alone there
 OBJ_DIR = os.path.join(CSRC, "build")
 
 
@@ -62,7 +63,7 @@ def compile_commands(extra_flags=(), obj_dir=None, parts=TU_PARTS):
     obj_dir = obj_dir or OBJ_DIR
     cc = [hipcc_path()] + [f for f in FLAGS if f != "-shared"] + list(extra_flags)
     cmds = []
-    for part in range(parts):
+    for part in range(parts + (SCAN_PARTS if parts > 1 else 0)):
         o = os.path.join(obj_dir, "etg_kernels.%d.o" % part)
         cmds.append((o, cc + ["-DETG_TU_PARTS=%d" % parts, "-DETG_TU_PART=%d" % part, "-c", "-o", o, os.path.join(CSRC, "etg_kernels.hip")]))
     for f in SOURCES[1:]:

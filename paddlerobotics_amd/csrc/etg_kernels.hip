@@ -21,7 +21,9 @@
 #include "etg_core16.h"
 #include "gram16.h"
 #include "policy_core.h"
+#include "scan_core.h"
 #include "../../include/etgsim_step_policy.h"
+#include "../../include/etgsim_scan_policy.h"
 #include "../../include/etgsim_collect.h"
 #include "../../include/etgsim_monitor.h"
 #include "../../include/etgsim_terminal.h"
@@ -1761,13 +1763,57 @@ struct StepPolOut {
 // the episode records of k_collect_policy16 (all NULL in the one-step kernels): the robot's running return and 1-based episode
 // step after the step and before a restart, and the bootstrap flag of the transition (replay.bootstrap_mask)
 struct EpOut { float* ret; int32_t* len; float* terminal; int bootstrap_from; };
+// SCAN (include/etgsim_scan_policy.h): the terrain height scan of scan_core.h computed by the wave itself.  The actor's last
+// n columns are the scan of the row it acts on, and act_obs / term_obs are wide rows [N, 49 + n]: the observation, then the scan.
+struct ScanPol {
+  const float* points;        // [n,2]
+  int n;                      // 1 .. kScanPolMax points: 4 n <= 64 lanes, one per (robot, point)
+  float offset, clip;
+  float* scan;                // [N,n] out: the scan columns of the rows the next step acts on
+};
+constexpr int kScanPolMax = 16;
+// the wave's scan state in LDS (752 bytes): the points, the scan of the 4 rows the step acts on and of the 4 rows it produced
+// (row stride kScanPolMax), the 4 robots' pose rows and which of them restarted
+struct ScanLds { float *pts, *acted, *term; scan::Row* row; float* rst; };
+// one point per lane: out[rob][j] of the robots whose pose row is in W.row; keep != NULL: only where W.rst says so, else keep's value
+__device__ __forceinline__ void scan4_eval(const KCfg& K, const ScanPol& Z, const ScanLds& W, int lane, float* out, const float* keep) {
+  if (lane < 4 * Z.n) {
+    const int r = lane / Z.n, j = lane - r * Z.n;
+    float v;
+    if (keep && W.rst[r] < 0.5f) v = keep[r * kScanPolMax + j];
+    else v = scan::scan_point(K, W.row[r], W.pts[2 * j], W.pts[2 * j + 1], Z.offset, Z.clip);
+    out[r * kScanPolMax + j] = v;
+  }
+}
+// launch prologue: the points, and the scan of the rows the first step acts on, from the live state in D.base (what
+// etg_height_scan reads: state_pose / make_row / scan_point) -- no input buffer that could be stale
+__device__ __forceinline__ void scan4_begin(const KCfg& K, const DevState& D, const ScanPol& Z, const ScanLds& W, int lane, int row0) {
+  if (lane < 2 * Z.n) W.pts[lane] = Z.points[lane];
+  if (lane < 4) {
+    float p[4];
+    scan::state_pose(D.base, K.n_env, row0 + lane, p);
+    W.row[lane] = scan::make_row(p, row0 + lane);
+  }
+  __syncthreads();
+  scan4_eval(K, Z, W, lane, W.acted, nullptr);
+  __syncthreads();
+}
+// launch epilogue: the scan columns of the rows the next step acts on
+__device__ __forceinline__ void scan4_end(const ScanPol& Z, const ScanLds& W, int lane, int row0) {
+  if (lane < 4 * Z.n) {
+    const int r = lane / Z.n, j = lane - r * Z.n;
+    Z.scan[(size_t)row0 * Z.n + lane] = W.acted[r * kScanPolMax + j];
+  }
+}
 // LOOP (k_collect_policy16 calls the body once per control step): the lane and block indices go through an empty asm, so what the
 // body derives from them is formed anew in every iteration instead of being hoisted and kept in registers through the ticks
-template <bool FLAT, bool KNEE, bool PLAIN, bool AUTO, bool LOOP = false>
+template <bool FLAT, bool KNEE, bool PLAIN, bool AUTO, bool LOOP = false, bool SCAN = false>
 __device__ __forceinline__ void step_policy16_body(const KCfg& K, const DevState& D, const PolicyW& P, float act_scale, float* obs,
                                                    const StepPolOut& O, const NextDyn& NX, float* lds_par, float* obs4, float* abuf,
                                                    float* hA, float* hB, float* part, float (*act4)[16],
-                                                   const EpOut E = EpOut{nullptr, nullptr, nullptr, 0}) {
+                                                   const EpOut E = EpOut{nullptr, nullptr, nullptr, 0},
+                                                   const ScanPol Z = ScanPol{nullptr, 0, 0.0f, 0.0f, nullptr},
+                                                   const ScanLds W = ScanLds{nullptr, nullptr, nullptr, nullptr, nullptr}) {
   using namespace pol;
   int lane = threadIdx.x;
   int blk = xcd_contiguous_block();                   // 4 robots; the host guarantees N % 16 == 0 (the grid is N / 4 exactly)
@@ -1778,12 +1824,24 @@ __device__ __forceinline__ void step_policy16_body(const KCfg& K, const DevState
   wave_ring_start(ring, P.w1, lane);                  // the first k-groups of layer 1 arrive while the rows are staged
   for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) obs4[idx] = obs[row0 * ETG_OBS_DIM + idx];
   __syncthreads();
-  for (int idx = lane; idx < 4 * WS; idx += 64) {
-    const int r = idx / WS, col = idx - r * WS;
-    abuf[idx] = col < P.in_dim ? obs4[r * ETG_OBS_DIM + P.col0 + col] : 0.0f;
+  if constexpr (SCAN) {                               // (W.acted: the launch prologue's, or the previous iteration's)
+    const int nobs = P.in_dim - Z.n, wide = ETG_OBS_DIM + Z.n;
+    for (int idx = lane; idx < 4 * WS; idx += 64) {
+      const int r = idx / WS, col = idx - r * WS;
+      abuf[idx] = col < nobs ? obs4[r * ETG_OBS_DIM + P.col0 + col] : col < P.in_dim ? W.acted[r * kScanPolMax + col - nobs] : 0.0f;
+    }
+    for (int idx = lane; idx < 4 * wide; idx += 64) {
+      const int r = idx / wide, col = idx - r * wide;
+      O.act_obs[row0 * wide + idx] = col < ETG_OBS_DIM ? obs4[r * ETG_OBS_DIM + col] : W.acted[r * kScanPolMax + col - ETG_OBS_DIM];
+    }
+  } else {
+    for (int idx = lane; idx < 4 * WS; idx += 64) {
+      const int r = idx / WS, col = idx - r * WS;
+      abuf[idx] = col < P.in_dim ? obs4[r * ETG_OBS_DIM + P.col0 + col] : 0.0f;
+    }
+    if (O.act_obs)
+      for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) O.act_obs[row0 * ETG_OBS_DIM + idx] = obs4[idx];
   }
-  if (O.act_obs)
-    for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) O.act_obs[row0 * ETG_OBS_DIM + idx] = obs4[idx];
   __syncthreads();
   HeadW hw;
   wave_hidden12(abuf, hA, hB, ring, P.w1, P.b1, P.b2, hw, P.w3, lane);
@@ -1831,11 +1889,33 @@ __device__ __forceinline__ void step_policy16_body(const KCfg& K, const DevState
     E.len[c.env] = len;
     E.terminal[c.env] = (len >= E.bootstrap_from || d <= 0.5f) ? 1.0f : 0.0f;
   }
+  // SCAN: the scan of the pose the step produced, from the state itself (what store_state16 is about to write to D.base)
+  if constexpr (SCAN)
+    if (c.r == 0) W.row[lane >> 4] = scan::row_of_base(L.p.x, L.p.y, L.p.z, L.qx, L.qy, L.qz, L.qw, c.env);
   __syncthreads();
-  for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) O.term_obs[row0 * ETG_OBS_DIM + idx] = obs4[idx];
+  if constexpr (SCAN) {
+    scan4_eval(K, Z, W, lane, W.term, nullptr);
+    __syncthreads();
+    const int wide = ETG_OBS_DIM + Z.n;
+    for (int idx = lane; idx < 4 * wide; idx += 64) {
+      const int r = idx / wide, col = idx - r * wide;
+      O.term_obs[row0 * wide + idx] = col < ETG_OBS_DIM ? obs4[r * ETG_OBS_DIM + col] : W.term[r * kScanPolMax + col - ETG_OBS_DIM];
+    }
+  } else {
+    for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) O.term_obs[row0 * ETG_OBS_DIM + idx] = obs4[idx];
+  }
   if (AUTO) {
     __syncthreads();                                  // the rows are read before a restart writes its reset row over them
     if (d > 0.5f) restart16(c, K, D, NX, L, obs4);    // whole 16-lane rows take this branch together (d is the robot's)
+  }
+  if constexpr (SCAN) {   // the next step's acted scan: the step's own, or -- a restarted robot -- the scan of its reset state
+    const bool rst = AUTO && d > 0.5f;
+    if (c.r == 0) {
+      W.rst[lane >> 4] = rst ? 1.0f : 0.0f;
+      if (rst) W.row[lane >> 4] = scan::row_of_base(L.p.x, L.p.y, L.p.z, L.qx, L.qy, L.qz, L.qw, c.env);
+    }
+    __syncthreads();
+    scan4_eval(K, Z, W, lane, W.acted, W.term);
   }
   store_state16(c, D.base, D.leg, L);
   if (c.r == 0) {
@@ -1845,6 +1925,13 @@ __device__ __forceinline__ void step_policy16_body(const KCfg& K, const DevState
   __syncthreads();
   for (int idx = lane; idx < 4 * ETG_OBS_DIM; idx += 64) obs[row0 * ETG_OBS_DIM + idx] = obs4[idx];
 }
+#define ETG_SCAN_POLICY16_LDS                                                                \
+  __shared__ float scan_pts[2 * kScanPolMax];                                                \
+  __shared__ float scan_acted[4 * kScanPolMax];                                              \
+  __shared__ float scan_term[4 * kScanPolMax];                                               \
+  __shared__ scan::Row scan_row[4];                                                          \
+  __shared__ float scan_rst[4];                                                              \
+  const ScanLds W = {scan_pts, scan_acted, scan_term, scan_row, scan_rst};
 #define ETG_STEP_POLICY16_LDS                                                                \
   __shared__ float lds_par[LDS16_FIELDS * BLOCK];                                            \
   __shared__ __attribute__((aligned(16))) float obs4[4 * ETG_OBS_DIM];                       \
@@ -1862,6 +1949,29 @@ template <bool FLAT, bool KNEE, bool PLAIN>
 __global__ void __launch_bounds__(BLOCK) k_step_policy16_ar(KCfg K, DevState D, PolicyW P, float act_scale, float* obs, StepPolOut O, NextDyn NX) {
   ETG_STEP_POLICY16_LDS
   step_policy16_body<FLAT, KNEE, PLAIN, true>(K, D, P, act_scale, obs, O, NX, lds_par, obs4, abuf, hA, hB, part, act4);
+}
+// ... with the scan columns (include/etgsim_scan_policy.h): the same body with SCAN, between the prologue that scans the live
+// state and the epilogue that hands the next step's scan columns out
+template <bool FLAT, bool KNEE, bool PLAIN>
+__global__ void __launch_bounds__(BLOCK) k_step_policy16_scan(KCfg K, DevState D, PolicyW P, float act_scale, float* obs, StepPolOut O, ScanPol Z) {
+  ETG_STEP_POLICY16_LDS
+  ETG_SCAN_POLICY16_LDS
+  const int row0 = xcd_contiguous_block() * 4;
+  scan4_begin(K, D, Z, W, threadIdx.x, row0);
+  step_policy16_body<FLAT, KNEE, PLAIN, false, false, true>(K, D, P, act_scale, obs, O, NextDyn{nullptr, nullptr, nullptr}, lds_par, obs4, abuf, hA,
+                                                            hB, part, act4, EpOut{nullptr, nullptr, nullptr, 0}, Z, W);
+  scan4_end(Z, W, threadIdx.x, row0);                 // (the body ends behind a __syncthreads() that follows its last write of W.acted)
+}
+template <bool FLAT, bool KNEE, bool PLAIN>
+__global__ void __launch_bounds__(BLOCK) k_step_policy16_scan_ar(KCfg K, DevState D, PolicyW P, float act_scale, float* obs, StepPolOut O, NextDyn NX,
+                                                                 ScanPol Z) {
+  ETG_STEP_POLICY16_LDS
+  ETG_SCAN_POLICY16_LDS
+  const int row0 = xcd_contiguous_block() * 4;
+  scan4_begin(K, D, Z, W, threadIdx.x, row0);
+  step_policy16_body<FLAT, KNEE, PLAIN, true, false, true>(K, D, P, act_scale, obs, O, NX, lds_par, obs4, abuf, hA, hB, part, act4,
+                                                           EpOut{nullptr, nullptr, nullptr, 0}, Z, W);
+  scan4_end(Z, W, threadIdx.x, row0);
 }
 
 // ---- etg_collect_policy (include/etgsim_collect.h): n_steps closed-loop control steps WITH restarts in one launch.  A wave
@@ -1900,6 +2010,29 @@ __global__ void __launch_bounds__(BLOCK) k_collect_policy16(KCfg K, DevState D, 
     __syncthreads();                                  // the rows of obs4 are out before the next iteration stages them again
   }
 }
+// ... with the scan columns: rec obs / next_obs are wide rows [K,N,49+n], and the 4 x n values of W.acted are carried from one
+// iteration to the next in LDS, as the rows of obs4 are carried in `obs`
+template <bool FLAT, bool KNEE, bool PLAIN>
+__global__ void __launch_bounds__(BLOCK) k_collect_policy16_scan(KCfg K, DevState D, PolicyW P, float act_scale, float* obs, CollectOut R,
+                                                                  int n_steps, int bootstrap_from, ScanPol Z) {
+  ETG_STEP_POLICY16_LDS
+  ETG_SCAN_POLICY16_LDS
+  const size_t N = K.n_env, wide = ETG_OBS_DIM + Z.n;
+  const int row0 = xcd_contiguous_block() * 4;
+  scan4_begin(K, D, Z, W, threadIdx.x, row0);
+  for (int s = 0; s < n_steps; s++) {
+    const size_t at = (size_t)s * N;
+    const StepPolOut O = {R.noise ? R.noise + at * ETG_ACT_DIM : nullptr, R.w3s, R.b3s, R.donef ? R.donef + at : nullptr,
+                          R.act + at * ETG_ACT_DIM, R.obs + at * wide, R.next_obs + at * wide, R.rew + at, R.done + at,
+                          R.info ? R.info + at * ETG_INFO_DIM : nullptr};
+    step_policy16_body<FLAT, KNEE, PLAIN, true, true, true>(K, D, P, act_scale, obs, O, NextDyn{nullptr, nullptr, nullptr}, lds_par, obs4, abuf, hA,
+                                                            hB, part, act4, EpOut{R.ep_ret + at, R.ep_len + at, R.terminal + at, bootstrap_from},
+                                                            Z, W);
+    __syncthreads();
+  }
+  scan4_end(Z, W, threadIdx.x, row0);
+}
+#undef ETG_SCAN_POLICY16_LDS
 #undef ETG_STEP_POLICY16_LDS
 
 // Closed loop on the 4-lanes-per-robot mapping (the mapping of every batch above 4096 robots): a workgroup of 4 waves owns
@@ -2232,6 +2365,9 @@ __global__ void __launch_bounds__(256) k_term_ctx(KCfg K, DevState D, const uint
 #define ETG_ARGS_STEP_POLICY KCfg, DevState, PolicyW, float, float*, StepPolOut
 #define ETG_ARGS_STEP_POLICY_AR KCfg, DevState, PolicyW, float, float*, StepPolOut, NextDyn
 #define ETG_ARGS_COLLECT KCfg, DevState, PolicyW, float, float*, CollectOut, int, int
+#define ETG_ARGS_STEP_POLICY_SCAN KCfg, DevState, PolicyW, float, float*, StepPolOut, ScanPol
+#define ETG_ARGS_STEP_POLICY_SCAN_AR KCfg, DevState, PolicyW, float, float*, StepPolOut, NextDyn, ScanPol
+#define ETG_ARGS_COLLECT_SCAN KCfg, DevState, PolicyW, float, float*, CollectOut, int, int, ScanPol
 #if ETG_TU_PARTS > 1
 #define ETG_SLOT_OWNER(S) (1 + ((S) - 1) % (ETG_TU_PARTS - 1))
 #if ETG_SLOT_OWNER(1) == ETG_TU_PART
@@ -2269,8 +2405,37 @@ __global__ void __launch_bounds__(256) k_term_ctx(KCfg K, DevState D, const uint
 #else
 #define ETG_TPL_7 extern template
 #endif
+// Slots 8..10 belong to parts ETG_TU_PARTS .. ETG_TU_PARTS + 2, which hold nothing else: the closed-loop kernels with SCAN
+// (ETG_SCAN_INST16 below).  In a part of their neighbours they would add callers of the heightfield functions to its module, and
+// the compiler then schedules that part's non-FLAT tick kernels differently (seen in 4 of them, k_rollout16 among them) -- the
+// existing kernels are to stay the instruction streams they are.
+#if ETG_TU_PARTS == ETG_TU_PART
+#define ETG_TPL_8 template
+#else
+#define ETG_TPL_8 extern template
+#endif
+#if ETG_TU_PARTS + 1 == ETG_TU_PART
+#define ETG_TPL_9 template
+#else
+#define ETG_TPL_9 extern template
+#endif
+#if ETG_TU_PARTS + 2 == ETG_TU_PART
+#define ETG_TPL_10 template
+#else
+#define ETG_TPL_10 extern template
+#endif
 // 16-lane families: <FLAT, KNEE, PLAIN> in the order of ETG_VARIANTS16 (etg_layout.h)
 #define ETG_INST16(KERN, S0, S1, S2, S3, S4, S5, ...)                          \
+  ETG_TPL_##S0 __global__ void KERN<true, true, true>(__VA_ARGS__);            \
+  ETG_TPL_##S1 __global__ void KERN<true, false, true>(__VA_ARGS__);           \
+  ETG_TPL_##S2 __global__ void KERN<true, true, false>(__VA_ARGS__);           \
+  ETG_TPL_##S3 __global__ void KERN<false, true, true>(__VA_ARGS__);           \
+  ETG_TPL_##S4 __global__ void KERN<false, false, true>(__VA_ARGS__);          \
+  ETG_TPL_##S5 __global__ void KERN<false, true, false>(__VA_ARGS__);
+// the same six variants for the SCAN kernels, in a table of their own: their slots are the parts of their own (above), and the
+// variant x entry-point matrix of the physics parity suite (tests/variant_matrix.py), which reads the ETG_INST* rows, has no
+// cell for them -- the scan kernels run the tick code of k_step_policy16* / k_collect_policy16, whose cells it has
+#define ETG_SCAN_INST16(KERN, S0, S1, S2, S3, S4, S5, ...)                     \
   ETG_TPL_##S0 __global__ void KERN<true, true, true>(__VA_ARGS__);            \
   ETG_TPL_##S1 __global__ void KERN<true, false, true>(__VA_ARGS__);           \
   ETG_TPL_##S2 __global__ void KERN<true, true, false>(__VA_ARGS__);           \
@@ -2316,6 +2481,9 @@ ETG_INST4(k_rollout, 2, 3, 4, 5, 6, 7, 1, 2, ETG_ARGS_ROLLOUT)
 ETG_INST4(k_rollout_actions, 3, 4, 5, 6, 7, 1, 2, 3, ETG_ARGS_TAPE)
 ETG_INSTP4(k_rollout_policy4, false, 4, 5, 6, 7, 1, 2, ETG_ARGS_POLICY)
 ETG_INSTP4(k_rollout_policy4, true, 3, 4, 5, 6, 7, 1, ETG_ARGS_POLICY)
+ETG_SCAN_INST16(k_step_policy16_scan, 8, 9, 10, 8, 9, 10, ETG_ARGS_STEP_POLICY_SCAN)
+ETG_SCAN_INST16(k_step_policy16_scan_ar, 9, 10, 8, 9, 10, 8, ETG_ARGS_STEP_POLICY_SCAN_AR)
+ETG_SCAN_INST16(k_collect_policy16_scan, 10, 8, 9, 10, 8, 9, ETG_ARGS_COLLECT_SCAN)
 #endif   // ETG_TU_PARTS > 1
 
 }  // namespace etg
@@ -2990,13 +3158,14 @@ extern "C" int etg_rollout_actions(EtgHandle* h, const float* actions, int n_ste
 
 // ---- the closed-loop entry points (etg_rollout_policy, etg_rollout_policy_record, etg_step_policy): what they ask of the
 // policy, and the two forms its weights are handed to the kernels in.  fn: the entry point's name for the error text
-static int policy_checks(const char* fn, const EtgHandle* h, const EtgPolicy* pol, int obs_col0) {
+// n_scan: the actor's last n_scan columns are scan columns the kernel computes itself (include/etgsim_scan_policy.h)
+static int policy_checks(const char* fn, const EtgHandle* h, const EtgPolicy* pol, int obs_col0, int n_scan = 0) {
   // (a wider policy -- etg_policy_create takes up to 512 columns -- has neither the 4 k-blocks of w1 nor the per-wave stream)
   if (pol->in_dim > 4 * pol::KQ1)
     return fail(ETG_ERR_BAD_ARG, std::string(fn) + ": the fused closed-loop kernels take a policy of in_dim <= 64 (wider ones: "
                                                    "etg_policy_forward / etg_policy_sample, then etg_step)");
   if (pol->device != h->device) return fail(ETG_ERR_BAD_ARG, std::string(fn) + ": policy and simulator live on different devices");
-  if (obs_col0 < 0 || obs_col0 + pol->in_dim > ETG_OBS_DIM || pol->out_dim != ETG_ACT_DIM)
+  if (obs_col0 < 0 || obs_col0 + pol->in_dim - n_scan > ETG_OBS_DIM || pol->out_dim != ETG_ACT_DIM)
     return fail(ETG_ERR_BAD_ARG, std::string(fn) + ": the policy must map observation columns [col0, col0 + in_dim) to 12 actions");
   return ETG_OK;
 }
@@ -3093,10 +3262,11 @@ extern "C" int etg_rollout_policy_record(EtgHandle* h, EtgPolicy* pol, int n_ste
 
 // The refusals that etg_step_policy and the collect entry points share, in this order (k_step_policy16 / k_collect_policy16 run
 // the fp32 per-wave actor tile only; policy_checks has already refused a policy wider than its 64 columns)
-static int step_policy_checks(const char* fn_, const EtgHandle* h, const EtgPolicy* pol, int precision, int obs_col0, const float* noise) {
+static int step_policy_checks(const char* fn_, const EtgHandle* h, const EtgPolicy* pol, int precision, int obs_col0, const float* noise,
+                              int n_scan = 0) {
   const std::string fn(fn_);
   if (noise && !pol->has_std) return fail(ETG_ERR_STATE, fn + ": sampling needs etg_policy_load_std() first");
-  if (int rc = policy_checks(fn_, h, pol, obs_col0)) return rc;
+  if (int rc = policy_checks(fn_, h, pol, obs_col0, n_scan)) return rc;
   if (precision != 0) return fail(ETG_ERR_BAD_ARG, fn + ": the kernel runs the fp32 per-wave actor tile: precision 0, in_dim <= 64");
   if (h->lanes != 16 || h->N % 16 != 0)
     return fail(ETG_ERR_BAD_ARG, fn + ": needs the 16-lanes-per-robot mapping and num_envs % 16 == 0");
@@ -3136,20 +3306,70 @@ extern "C" int etg_step_policy(EtgHandle* h, EtgPolicy* pol, float act_scale, in
   return ETG_OK;
 }
 
+// The refusals the scan columns add to those of step_policy_checks (include/etgsim_scan_policy.h), before them and before any
+// launch.  `wide`: are the wide row arrays all there?
+static int scan_policy_checks(const char* fn_, const EtgHandle* h, const EtgPolicy* pol, const float* points, int n_points, float clip,
+                              const float* scan, bool wide) {
+  const std::string fn(fn_);
+  if (!points || !scan || !wide) return fail(ETG_ERR_BAD_ARG, fn + ": points, scan and the wide row arrays must be non-null");
+  if (n_points < 1 || n_points > kScanPolMax) return fail(ETG_ERR_BAD_ARG, fn + ": n_points must be in 1..16 (one lane per robot and point)");
+  if (pol->in_dim - n_points < 1) return fail(ETG_ERR_BAD_ARG, fn + ": the actor must read at least one observation column before its n_points scan columns");
+  if (pol->in_dim > 4 * pol::KQ1) return fail(ETG_ERR_BAD_ARG, fn + ": the actor's observation and scan columns together must be at most 64 (in_dim <= 64)");
+  if (clip < 0.0f) return fail(ETG_ERR_BAD_ARG, fn + ": clip must not be negative");
+  if (h->K.terrain != 0 && !h->K.hf) return fail(ETG_ERR_STATE, fn + ": call etg_set_heightfield first");
+  return ETG_OK;
+}
+
+// etg_step_policy with the scan columns computed in the launch (include/etgsim_scan_policy.h): k_step_policy16_scan / _scan_ar
+extern "C" int etg_step_policy_scan(EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int auto_reset,
+                                    const float* noise, const uint8_t* donef, float* obs, float* act, float* act_obs, float* terminal_obs,
+                                    float* reward, uint8_t* done, float* info, const float* points, int n_points, float offset, float clip,
+                                    float* scan, void* stream) {
+  CHECK_HANDLE(h);
+  if (!pol || !obs || !reward || !done)
+    return fail(ETG_ERR_BAD_ARG, "etg_step_policy_scan: policy, obs, reward and done must be non-null");
+  if (int rc = scan_policy_checks("etg_step_policy_scan", h, pol, points, n_points, clip, scan, act_obs && terminal_obs)) return rc;
+  if (!h->was_reset) return fail(ETG_ERR_STATE, "etg_step_policy_scan: call etg_reset first");
+  if (int rc = step_policy_checks("etg_step_policy_scan", h, pol, precision, obs_col0, noise, n_points)) return rc;
+  if (auto_reset) refresh_all_cached(h);
+  const bool fused_reset = auto_reset && h->all_cached;
+  advance_obs_stream(h, fused_reset ? 2 : 1);
+  const PolicyW Pq = policy_wave(pol, obs_col0);
+  const StepPolOut O = {noise, (const float4*)pol->w3sq, pol->b3s, donef, act, act_obs, terminal_obs, reward, done, info};
+  const ScanPol Z = {points, n_points, offset, clip, scan};
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g(h->N / 4);
+  if (fused_reset) {
+    LAUNCH16(k_step_policy16_scan_ar, g, s, h->K, h->D, Pq, act_scale, obs, O, h->NX, Z);
+  } else {
+    LAUNCH16(k_step_policy16_scan, g, s, h->K, h->D, Pq, act_scale, obs, O, Z);
+  }
+  HIP_TRY(hipGetLastError());
+  if (auto_reset && !fused_reset) {   // as etg_step_policy; the reset moved robots, so `scan` is taken again from the live state
+    if (h->push_on)
+      if (int rc = etg_clear_pushes(h, done, stream)) return rc;
+    if (int rc = etg_reset(h, done, obs, stream)) return rc;
+    HIP_TRY(etg_height_scan_launch(h->K, h->D.base, nullptr, nullptr, h->N, points, n_points, offset, clip, scan, s));
+  }
+  return ETG_OK;
+}
+
 // n_steps closed-loop control steps with restarts in one launch (include/etgsim_collect.h): k_collect_policy16.  Every refusal
 // comes before any launch and before any change to the handle.  etg_collect_policy records no info rows (rec_info = NULL);
 // etg_collect_policy_info (include/etgsim_monitor.h) is the same launch with CollectOut::info set.
 static int collect_policy_launch(const char* fn_, EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int n_steps,
                                  int bootstrap_from, const float* noise, const uint8_t* donef, float* obs, float* rec_obs,
                                  float* rec_action, float* rec_reward, uint8_t* rec_done, float* rec_next_obs, float* rec_terminal,
-                                 float* rec_ep_ret, int32_t* rec_ep_len, float* rec_info, void* stream) {
+                                 float* rec_ep_ret, int32_t* rec_ep_len, float* rec_info, void* stream, const ScanPol* Z = nullptr) {
   const std::string fn(fn_);
   CHECK_HANDLE(h);
-  if (!pol || !obs || !rec_obs || !rec_action || !rec_reward || !rec_done || !rec_next_obs || !rec_terminal || !rec_ep_ret || !rec_ep_len)
+  if (!pol || !obs || !rec_action || !rec_reward || !rec_done || !rec_terminal || !rec_ep_ret || !rec_ep_len || (!Z && (!rec_obs || !rec_next_obs)))
     return fail(ETG_ERR_BAD_ARG, fn + ": policy, obs and the eight record arrays must be non-null");
+  if (Z)   // the scan columns computed in the launch (include/etgsim_scan_policy.h): rec_obs / rec_next_obs are its wide rows
+    if (int rc = scan_policy_checks(fn_, h, pol, Z->points, Z->n, Z->clip, Z->scan, rec_obs && rec_next_obs)) return rc;
   if (n_steps < 1) return fail(ETG_ERR_BAD_ARG, fn + ": n_steps must be at least 1");
   if (!h->was_reset) return fail(ETG_ERR_STATE, fn + ": call etg_reset first");
-  if (int rc = step_policy_checks(fn_, h, pol, precision, obs_col0, noise)) return rc;
+  if (int rc = step_policy_checks(fn_, h, pol, precision, obs_col0, noise, Z ? Z->n : 0)) return rc;
   if (h->NX.ok)
     return fail(ETG_ERR_STATE, fn + ": the handle has prepared next-episode dynamics (etg_prepare_next_dynamics): a second "
                                "restart inside the launch would find no prepared row -- use etg_step_policy");
@@ -3163,7 +3383,11 @@ static int collect_policy_launch(const char* fn_, EtgHandle* h, EtgPolicy* pol, 
                         rec_next_obs, rec_terminal, rec_ep_ret, rec_ep_len, rec_info};
   hipStream_t s = (hipStream_t)stream;
   const dim3 g(h->N / 4);
-  LAUNCH16(k_collect_policy16, g, s, h->K, h->D, Pq, act_scale, obs, R, n_steps, bootstrap_from);
+  if (Z) {
+    LAUNCH16(k_collect_policy16_scan, g, s, h->K, h->D, Pq, act_scale, obs, R, n_steps, bootstrap_from, *Z);
+  } else {
+    LAUNCH16(k_collect_policy16, g, s, h->K, h->D, Pq, act_scale, obs, R, n_steps, bootstrap_from);
+  }
   HIP_TRY(hipGetLastError());
   return ETG_OK;
 }
@@ -3186,6 +3410,18 @@ extern "C" int etg_collect_policy_info(EtgHandle* h, EtgPolicy* pol, float act_s
   return collect_policy_launch("etg_collect_policy_info", h, pol, act_scale, precision, obs_col0, n_steps, bootstrap_from, noise, donef,
                                obs, rec_obs, rec_action, rec_reward, rec_done, rec_next_obs, rec_terminal, rec_ep_ret, rec_ep_len, rec_info,
                                stream);
+}
+
+// etg_collect_policy_info (rec_info may be NULL here) with the scan columns computed in the launch (include/etgsim_scan_policy.h)
+extern "C" int etg_collect_policy_scan(EtgHandle* h, EtgPolicy* pol, float act_scale, int precision, int obs_col0, int n_steps,
+                                       int bootstrap_from, const float* noise, const uint8_t* donef, float* obs, float* rec_obs,
+                                       float* rec_action, float* rec_reward, uint8_t* rec_done, float* rec_next_obs,
+                                       float* rec_terminal, float* rec_ep_ret, int32_t* rec_ep_len, float* rec_info, const float* points,
+                                       int n_points, float offset, float clip, float* scan, void* stream) {
+  const ScanPol Z = {points, n_points, offset, clip, scan};
+  return collect_policy_launch("etg_collect_policy_scan", h, pol, act_scale, precision, obs_col0, n_steps, bootstrap_from, noise, donef,
+                               obs, rec_obs, rec_action, rec_reward, rec_done, rec_next_obs, rec_terminal, rec_ep_ret, rec_ep_len, rec_info,
+                               stream, &Z);
 }
 
 extern "C" int etg_leg_kinematics(EtgHandle* h, const float* q, int n, float* foot, float* jac, void* stream) {

@@ -48,6 +48,13 @@ ETG_HD Row make_row(const float* pose, int env) {
   return r;
 }
 
+// the row of a robot whose seven base values the caller holds (the closed-loop kernels with SCAN, etg_kernels.hip: the state is
+// in registers there, before it is stored): state_pose's arithmetic on them, then make_row
+ETG_HD Row row_of_base(float px, float py, float pz, float qx, float qy, float qz, float qw, int env) {
+  const float pose[4] = {px, py, pz, yaw_of_quat(qx, qy, qz, qw)};
+  return make_row(pose, env);
+}
+
 ETG_HD float quiet_nan() {   // (a bit pattern: the library is built with -ffinite-math-only)
   const unsigned u = 0x7fc00000u;
   float f;

@@ -248,9 +248,12 @@ class BatchedQuadrupedEnv:
         # the terrain height scan (heightscan.py, include/etgsim_heightscan.h): height_scan=dict(xs=, ys=, offset=, clip=) sets the
         # grid of scan_pose() / height_scan() / height_scan_at(); sensor_mode["height_scan"] appends its P columns to the view
         hs = dict(height_scan or {})
-        unknown = set(hs) - {"xs", "ys", "offset", "clip"}
+        unknown = set(hs) - {"xs", "ys", "offset", "clip", "fused"}
         if unknown:
-            raise ValueError("height_scan has the keys xs, ys, offset and clip, not %s" % ", ".join(sorted(unknown)))
+            raise ValueError("height_scan has the keys xs, ys, offset, clip and fused, not %s" % ", ".join(sorted(unknown)))
+        # fused=True: step_policy / collect_policy compute the scan columns inside their launch (include/etgsim_scan_policy.h)
+        # instead of refusing a scan env.  It changes no state and is not part of the env digest.
+        self._scan_fused = bool(hs.get("fused", False))
         self._scan_grid = _hs.scan_grid(hs.get("xs", _hs.DEFAULT_XS), hs.get("ys", _hs.DEFAULT_YS))
         self._scan_offset, self._scan_clip = float(hs.get("offset", _hs.DEFAULT_OFFSET)), float(hs.get("clip", _hs.DEFAULT_CLIP))
         self._scan_P = len(self._scan_grid) if (sensor_mode or {}).get("height_scan") else 0
@@ -894,6 +897,30 @@ class BatchedQuadrupedEnv:
                 info["terminal_obs"] = self._last_view
         return (self._last_view, self.reward, self.done.view(torch.bool) if want_info else self.done, info)
 
+    def _scan_args(self):
+        """points, n_points, offset, clip, scan of etg_step_policy_scan / etg_collect_policy_scan (include/etgsim_scan_policy.h)"""
+        if self._scan_buf is None:
+            self._scan_buf = torch.zeros(self.num_envs, self._scan_P, device=self.device)
+        return (_ptr(self._scan_points(None)), int(self._scan_P), C.c_float(self._scan_offset), C.c_float(self._scan_clip),
+                _ptr(self._scan_buf))
+
+    def _wide_idx(self):
+        """the view's columns within the rows step_policy / collect_policy get back: sensor_mode's selection of the 49, and on
+        a scan env the P scan columns behind them (wide rows [.., 49+P]); None: the rows are the view"""
+        if self._col_idx is None:
+            return None
+        if self._scan_P and getattr(self, "_wcol_idx", None) is None:
+            tail = torch.arange(A.OBS_DIM, A.OBS_DIM + self._scan_P, device=self.device)
+            self._wcol_idx = torch.cat([self._col_idx, tail])
+        return self._wcol_idx if self._scan_P else self._col_idx
+
+    def _fused_view(self):
+        """the view after step_policy / collect_policy: on a scan env env.obs's columns and the scan columns the launch
+        returned (no etg_height_scan launch)"""
+        if not self._scan_P:
+            return self._obs_view()
+        return torch.cat([self._row_view(self.obs, None), self._scan_buf], dim=1)
+
     def _step_policy_refusal(self, policy, precision):
         """why step_policy's kernel does not cover this env / policy (None: it does)"""
         contiguous = self._cols == list(range(self._cols[0], self._cols[0] + len(self._cols)))
@@ -907,13 +934,20 @@ class BatchedQuadrupedEnv:
             return "observation history (sensor_mode['RNN']) is not covered"
         if self._xcols:
             return "extra sensor columns are not covered"
-        if self._scan_P:
+        if self._scan_P and not self._scan_fused:
             return "height scan columns are not covered (sensor_mode['height_scan']: step() appends them after the launch)"
         if getattr(self, "_noise_on", False):
             return "sensor noise is not covered"
         if self._rand_force:
             return "random pushes are not covered"
-        if not contiguous or policy.obs_dim != len(self._cols) or policy.action_dim != A.NUM_MOTORS:
+        if self._scan_P:   # height_scan=dict(fused=True): the launch computes the scan columns, the actor's last P inputs
+            if len(self._cols) + self._scan_P > 64:
+                return ("the view has %d observation + %d scan columns: more than the 64 the per-wave actor tile takes"
+                        % (len(self._cols), self._scan_P))
+            if not contiguous or policy.obs_dim != len(self._cols) + self._scan_P or policy.action_dim != A.NUM_MOTORS:
+                return ("height scan columns are not covered by this policy: it has %d inputs, the view has the env's (contiguous) "
+                        "%d observation columns and then %d scan columns" % (policy.obs_dim, len(self._cols), self._scan_P))
+        elif not contiguous or policy.obs_dim != len(self._cols) or policy.action_dim != A.NUM_MOTORS:
             return "the policy must map the env's (contiguous) observation columns to 12 actions"
         if int(precision) != 0:
             return "precision must be 0 (the fp32 actor)"
@@ -948,16 +982,20 @@ class BatchedQuadrupedEnv:
         df = self._donef_bytes(donef)
         if getattr(self, "_sp_buf", None) is None:
             z = lambda *shape: torch.zeros(*shape, device=self.device)
-            self._sp_buf = (z(N, A.NUM_MOTORS), z(N, A.OBS_DIM), z(N, A.OBS_DIM))
+            self._sp_buf = (z(N, A.NUM_MOTORS), z(N, A.OBS_DIM + self._scan_P), z(N, A.OBS_DIM + self._scan_P))
         act, act_obs, term = self._sp_buf
         fused_reset = self.auto_reset and (not self._rand_dyn or self._nx_on)   # as in step()
-        _lib.check(self._lib.etg_step_policy(self._h, policy._h, C.c_float(act_scale), int(precision), int(self._cols[0]),
-                                             int(fused_reset), _ptr(noise), _ptr(df), _ptr(self.obs), _ptr(act), _ptr(act_obs),
-                                             _ptr(term), _ptr(self.reward), _ptr(self.done),
-                                             _ptr(self.info_buf) if want_info else None, self._stream()))
+        args = (self._h, policy._h, C.c_float(act_scale), int(precision), int(self._cols[0]), int(fused_reset), _ptr(noise), _ptr(df),
+                _ptr(self.obs), _ptr(act), _ptr(act_obs), _ptr(term), _ptr(self.reward), _ptr(self.done),
+                _ptr(self.info_buf) if want_info else None)
+        if self._scan_P:   # wide rows [N,49+P] and the next view's scan columns from the launch itself
+            _lib.check(self._lib.etg_step_policy_scan(*args, *self._scan_args(), self._stream()))
+        else:
+            _lib.check(self._lib.etg_step_policy(*args, self._stream()))
         self._keep_step = (noise, df)
         info = self._info() if want_info else {}
-        sel = (lambda o: o) if self._col_idx is None else (lambda o: o.index_select(1, self._col_idx))
+        idx = self._wide_idx()
+        sel = (lambda o: o) if idx is None else (lambda o: o.index_select(1, idx))
         info["terminal_obs"] = sel(term)
         info["acted_obs"] = sel(act_obs)
         if self.auto_reset:
@@ -966,7 +1004,7 @@ class BatchedQuadrupedEnv:
             self._reset_mask = self.done.clone()
             self.reset(env_ids=self._reset_mask, _keep_offsets=True)
         else:
-            self._last_view = self._obs_view()
+            self._last_view = self._fused_view()
         if self._nx_on:
             self._refresh_next_dynamics()
         return (self._last_view, self.reward, self.done.view(torch.bool) if want_info else self.done, info, act)
@@ -1020,17 +1058,22 @@ class BatchedQuadrupedEnv:
         bufs = getattr(self, "_cp_buf", None)
         if bufs is None or bufs["reward"].shape[0] != K:
             z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=self.device)
-            bufs = self._cp_buf = {"obs": z(K, N, A.OBS_DIM), "action": z(K, N, A.NUM_MOTORS), "reward": z(K, N),
-                                   "done": z(K, N, dtype=torch.uint8), "next_obs": z(K, N, A.OBS_DIM), "terminal": z(K, N),
+            wide = A.OBS_DIM + self._scan_P
+            bufs = self._cp_buf = {"obs": z(K, N, wide), "action": z(K, N, A.NUM_MOTORS), "reward": z(K, N),
+                                   "done": z(K, N, dtype=torch.uint8), "next_obs": z(K, N, wide), "terminal": z(K, N),
                                    "ep_ret": z(K, N), "ep_len": z(K, N, dtype=torch.int32)}
         from .replay import BOOTSTRAP_ALWAYS_FROM
         args = (self._h, policy._h, C.c_float(act_scale), 0, int(self._cols[0]), K, int(BOOTSTRAP_ALWAYS_FROM), _ptr(noise), _ptr(donef),
                 _ptr(self.obs), _ptr(bufs["obs"]), _ptr(bufs["action"]), _ptr(bufs["reward"]), _ptr(bufs["done"]), _ptr(bufs["next_obs"]),
                 _ptr(bufs["terminal"]), _ptr(bufs["ep_ret"]), _ptr(bufs["ep_len"]))
+        ibuf = None
         if want_info:
             ibuf = getattr(self, "_cp_info", None)
             if ibuf is None or ibuf.shape[0] != K:
                 ibuf = self._cp_info = torch.zeros(K, N, A.INFO_DIM, device=self.device)
+        if self._scan_P:   # wide records [K,N,49+P] and the next view's scan columns from the launch itself
+            rc = self._lib.etg_collect_policy_scan(*args, _ptr(ibuf), *self._scan_args(), self._stream())
+        elif want_info:
             rc = self._lib.etg_collect_policy_info(*args, _ptr(ibuf), self._stream())
         else:
             rc = self._lib.etg_collect_policy(*args, self._stream())
@@ -1038,8 +1081,9 @@ class BatchedQuadrupedEnv:
             raise FusedKernelUnavailable("collect_policy: " + self._lib.etg_last_error().decode())
         _lib.check(rc)
         self._keep_step = (noise, donef)
-        self._last_view = self._obs_view()
-        sel = (lambda o: o) if self._col_idx is None else (lambda o: o.index_select(2, self._col_idx))
+        self._last_view = self._fused_view()
+        idx = self._wide_idx()
+        sel = (lambda o: o) if idx is None else (lambda o: o.index_select(2, idx))
         out = dict(bufs)
         out["obs"], out["next_obs"] = sel(bufs["obs"]), sel(bufs["next_obs"])
         out["done"] = bufs["done"].view(torch.bool)
